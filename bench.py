@@ -46,7 +46,7 @@ def _spawn_ranks(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
-HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
+HBM_PEAK_GBPS = 8000.0  # MI355X: 8 TB/s spec
 # float64 vector issue: one wave64 VALU instruction occupies a SIMD for 4 cycles (16 lanes / clk,
 # 78.6 TFLOP/s fp64 vector peak = 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz); fp32: 2 cycles
 SIMDS, CLOCK_HZ = 1024, 2.4e9
@@ -154,11 +154,52 @@ class _Ctx:
         self.__dict__.update(kw)
 
 
+DUMP_MAX_BYTES = 60 * 10**6       # (--dump-outputs promises at most 64 MB: room for the .npy headers)
+DUMP_SEED = 0
+
+
+def _dump_lanes(B: int, row_bytes: int) -> "np.ndarray":
+    """Lanes written by --dump-outputs: all of them when every field fits in DUMP_MAX_BYTES, else a fixed, seeded,
+    sorted sample (the same for every run with the same batch)."""
+    n = min(B, DUMP_MAX_BYTES // max(row_bytes, 1))
+    if n == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+
+
+def finite_lanes(snapshot: dict, lanes: "np.ndarray"):
+    """Drop the lanes whose state went non-finite: the kernel flags them (JM_LANE_NAN) and a caller truncates them
+    (envs.WalkerVecEnv.has_terminated); their rows are not results.  Returns (snapshot, lanes, number dropped)."""
+    import torch
+    keep = None
+    for t in snapshot.values():
+        ok = torch.isfinite(t.double()).all(0)
+        keep = ok if keep is None else keep & ok
+    if keep is None:
+        return snapshot, lanes, 0
+    keep_np = keep.cpu().numpy()
+    return ({k: t[:, keep] for k, t in snapshot.items()}, lanes[keep_np], int((~keep_np).sum()))
+
+
+def write_outputs(snapshot: dict, lanes: "np.ndarray", out_dir: str) -> None:
+    """`DIR/<field>.npy`, shape (rows, lanes) in the engine's float dtype (status as float64), plus `lanes.npy`."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in snapshot.items():
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    np.save(os.path.join(out_dir, "lanes.npy"), lanes.astype(np.float64))
+
+
 def measure(ctx, *, model_name: str, B: int, dtype, solver: str, contact_model: str, dt: float, steps: int, warmup: int,
-            episode: int, extra_terms: str, gather_obs: bool = False, strong: bool = False, headline: bool = False):
+            episode: int, extra_terms: str, gather_obs: bool = False, strong: bool = False, headline: bool = False,
+            dump_dir: str = None):
     """One timed workload on this rank's GPU: `warmup` untimed steps, then exactly `steps` steps between barriers
     (wall clock, max over ranks -> `value`) with every step launch timed by HIP events on the launch stream inside the
-    library (-> `roofline`).  Returns (JSON dict, the seeded states, the model)."""
+    library (-> `roofline`).  Returns (JSON dict, the seeded states, the model).
+    `dump_dir`: the outputs of the last timed step (every output field the engine binds, taken right after that step and
+    before any episode reset) of the lanes whose state stayed finite (`finite_lanes`) are written there by `write_outputs`."""
     import torch
     import torch.distributed as dist
 
@@ -207,11 +248,20 @@ def measure(ctx, *, model_name: str, B: int, dtype, solver: str, contact_model: 
     status_log = torch.zeros((n_log, B), dtype=torch.int32, device=device)
     n_logged = 0
     n_done = 0
+    snapshot = None
+    if dump_dir is not None:
+        # the output rows of the step (the engine also keeps solver state and scratch in `_fields`: not outputs)
+        dump_names = sorted(k for k in eng._fields if eng._rows.get(k, 0) > 0)
+        row_bytes = 8 * (1 + sum(eng.field(k).shape[0] for k in dump_names))     # (+ lanes.npy; at most 8 bytes a value)
+        dump_lanes = _dump_lanes(B, row_bytes)
+        dump_idx = torch.from_numpy(dump_lanes).to(device)
 
-    def one_step() -> None:
-        nonlocal n_done, n_logged
+    def one_step(last: bool = False) -> None:
+        nonlocal n_done, n_logged, snapshot
         eng.step(dt)
         n_done += 1
+        if last and dump_dir is not None:
+            snapshot = {k: eng.field(k).index_select(1, dump_idx) for k in dump_names}
         if episode > 0 and n_done % episode == 0:
             status_log[n_logged % n_log].copy_(eng.status.reshape(-1))
             n_logged += 1
@@ -237,8 +287,8 @@ def measure(ctx, *, model_name: str, B: int, dtype, solver: str, contact_model: 
     barrier()
     eng.enable_timing(os.environ.get("JM_BENCH_NO_EVENTS") != "1")   # (A/B of the cost of the per-launch HIP events: DESIGN.md section 12)
     t0 = time.perf_counter()
-    for _ in range(steps):
-        one_step()
+    for i in range(steps):
+        one_step(last=i == steps - 1)
     if gather is not None:
         # the timed region ends when the last gathered block has landed; how long that takes once the physics is done
         # is the part of the collectives the stepping did not hide (reported separately as `gather.exposed_ms`)
@@ -251,6 +301,11 @@ def measure(ctx, *, model_name: str, B: int, dtype, solver: str, contact_model: 
     elapsed = time.perf_counter() - t0
     n_launch, kernel_ms = eng.timing_summary()
     eng.enable_timing(False)
+    dump_info = None
+    if snapshot is not None and rank == 0:
+        snapshot, kept, dropped = finite_lanes(snapshot, dump_lanes)
+        write_outputs(snapshot, kept, dump_dir)
+        dump_info = {"dir": dump_dir, "lanes": int(len(kept)), "lanes_dropped_nonfinite": dropped}
     if world > 1 or getattr(ctx, "pg", False):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -401,6 +456,8 @@ def measure(ctx, *, model_name: str, B: int, dtype, solver: str, contact_model: 
                          "exposed_ms": 1e3 * gather_wait_s,
                          "note": "asynchronous all-gather on RCCL's stream, overlapped with the next steps; exposed_ms = "
                                  "wait for the collectives still in flight when the last step has finished"}
+    if dump_info is not None:
+        out["dump_outputs"] = dump_info
     if not headline:
         # compact form of a secondary workload
         out = {"workload": out["config"]["workload"], "model": model_name, "batch": B, "solver": solver, "dt": dt,
@@ -573,6 +630,10 @@ def main() -> None:
                          "fExternal and the contact forces are bound, so every launch runs the whole of "
                          "Engine::computeExtraTerms (engine.cc:800-905) like the reference does after every step; "
                          "'sensors': only what the sensors need (the round-3 headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (every output field of the engine, "
+                         "all lanes or a fixed seeded sample of them, at most 64 MB, less the lanes whose state went non-finite; "
+                         "their indices in DIR/lanes.npy) as DIR/<field>.npy")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary workloads (ANYmal euler + constraint model, Atlas spring-damper, "
                          "Atlas constraint model) appended as `secondary` to the JSON line at N = 1")
@@ -630,7 +691,7 @@ def main() -> None:
     out, states, model = measure(ctx, model_name=args.model, B=B, dtype=dtype, solver=args.solver,
                                  contact_model=args.contact_model, dt=args.dt, steps=args.steps, warmup=args.warmup,
                                  episode=args.episode, extra_terms=args.extra_terms, gather_obs=args.gather_obs,
-                                 strong=args.strong, headline=True)
+                                 strong=args.strong, headline=True, dump_dir=args.dump_outputs)
     if rank == 0:
         if world == 1 and not args.no_secondary and args.model == "anymal" and not constrained and args.dtype == "f64":
             out["secondary"] = secondary_workloads(ctx, args)

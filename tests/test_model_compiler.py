@@ -140,15 +140,18 @@ def test_builtin_models(name, nq, nv, nm, nc):
         assert m.mass[2] == pytest.approx(0.1) and np.allclose(m.com[2], [0, 0, 1.0])
 
 
+# numbers derived from the reference's URDF files by tools/make_urdf_fixtures.py (the files themselves are not part of
+# this repository)
+URDF_PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_urdf.npz")
+
+
 def test_builtin_models_match_the_reference_urdfs_when_present():
-    ref = "/root/reference/data/quadrupedal_robots/anymal/anymal.urdf"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not available on this machine")
-    from jiminy_amd.model import build_robot
-    m = build_robot(ref, has_freeflyer=True, name="anymal")
+    """The shipped anymal model is what `build_robot` makes of the reference's anymal.urdf (pinned in URDF_PINS)."""
+    pins = np.load(URDF_PINS)
     b = load_builtin("anymal")
-    assert m.topology_signature() == b.topology_signature()
-    assert np.array_equal(m.inertia, b.inertia) and np.array_equal(m.placement_R, b.placement_R)
+    assert str(pins["anymal_model_signature"]) == b.topology_signature()
+    assert np.array_equal(pins["anymal_model_inertia"], b.inertia)
+    assert np.array_equal(pins["anymal_model_placement_R"], b.placement_R)
 
 
 # ---- pins that do not go through CompiledModel's own construction: the URDF XML walked directly --------------
@@ -220,12 +223,7 @@ def _model_composite(m):
 
 
 # frozen from the reference's URDF files by `_urdf_composite` (total mass [kg], COM [m], diagonal of the
-# composite inertia about the root-link origin [kg m^2]); the XML itself is re-walked when the reference
-# tree is present
-URDF_COMPOSITES = {
-    "anymal": ("quadrupedal_robots/anymal/anymal.urdf", None),
-    "atlas": ("bipedal_robots/atlas/atlas.urdf", None),
-}
+# composite inertia about the root-link origin [kg m^2]); the whole of what the XML walk gives is in URDF_PINS
 FROZEN_COMPOSITES = {
     "anymal": (52.134849999999986, [-0.009001324210294755, -9.012968292868901e-05, -0.07019512926579306],
                [2.396821450925352, 6.452496555268907, 6.267118106699941]),
@@ -242,10 +240,8 @@ def test_composite_inertia_matches_the_urdf_xml(name):
     assert got[0] == pytest.approx(frozen[0], rel=1e-12)
     assert np.allclose(got[1], frozen[1], rtol=0, atol=1e-12)
     assert np.allclose(np.diag(got[2]), frozen[2], rtol=1e-12)
-    urdf = os.path.join(os.environ.get("JIMINY_REFERENCE", "/root/reference"), "data", URDF_COMPOSITES[name][0])
-    if not os.path.exists(urdf):
-        pytest.skip("reference URDF not available on this machine: checked against the frozen values only")
-    want = _urdf_composite(urdf)
+    pins = np.load(URDF_PINS)
+    want = (float(pins[f"{name}_mass"]), pins[f"{name}_com"], pins[f"{name}_inertia"])
     assert got[0] == pytest.approx(want[0], rel=1e-13)
     assert np.allclose(got[1], want[1], rtol=0, atol=1e-13)
     assert np.allclose(got[2], want[2], rtol=1e-12, atol=1e-12)

@@ -29,6 +29,8 @@ Two tiers, labelled per array group in the .npz (`tier__<group>`), in DESIGN.md 
           arrays are a second reading of those lines by the reference's own text, not a pin.
 
 Run in the build container:   python tools/make_ref_cpp_fixtures.py
+Check that the committed fixtures are what the reference's text computes (regenerated bit for bit, nothing written
+under tests/):   python tools/make_ref_cpp_fixtures.py --check
 Consumers: tests/test_reference_cpp_leaves.py (oracle on the CPU; HIP kernels through the C ABI with -m gpu).
 """
 from __future__ import annotations
@@ -906,5 +908,20 @@ def main(out_path: str = OUT) -> None:
     print(f"wrote {os.path.relpath(out_path, ROOT)}: {len(out)} arrays, {os.path.getsize(out_path)} bytes")
 
 
+def check() -> None:
+    """Regenerate into oracle/_ref/ and compare with the committed fixtures array by array, bytes included."""
+    os.makedirs(WORK, exist_ok=True)
+    again_path = os.path.join(WORK, "ref_cpp_leaves.again.npz")
+    main(again_path)
+    fix, again = np.load(OUT), np.load(again_path)
+    if set(again.files) != set(fix.files):
+        sys.exit(f"array names differ: {sorted(set(again.files) ^ set(fix.files))}")
+    bad = [k for k in fix.files if fix[k].dtype != again[k].dtype or fix[k].shape != again[k].shape
+           or fix[k].tobytes() != again[k].tobytes()]
+    if bad:
+        sys.exit(f"{len(bad)} arrays differ from {os.path.relpath(OUT, ROOT)}: {bad}")
+    print(f"{os.path.relpath(OUT, ROOT)}: all {len(fix.files)} arrays regenerate bit-identically")
+
+
 if __name__ == "__main__":
-    main()
+    check() if sys.argv[1:] == ["--check"] else main()
