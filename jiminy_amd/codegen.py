@@ -401,6 +401,39 @@ def is_stale(model: CompiledModel, variant: Optional[int] = None) -> bool:
     return any((not os.path.exists(d)) or os.path.getmtime(d) > t for d in deps)
 
 
+# the compile flags of every translation unit of a topology library (build_library adds the topology header and the
+# flags of the build variant); build_probe compiles the device-math probe of the tests with the same list
+COMMON_FLAGS = [f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
+                "-Wno-unused-value", "-ffp-contract=fast"]
+
+
+def build_probe(src: str, out: str, force: bool = False) -> str:
+    """Compile the test probe of jm_math.h (tests/device_math/jm_math_probe.hip) into the shared library `out`, with the
+    flags of a topology library of build variant 0.  Rebuilt when the digest of its sources and flags changes."""
+    import hashlib
+    flags = COMMON_FLAGS + list(BUILD_VARIANTS[0])
+    h = hashlib.sha256(" ".join(flags).encode())
+    for path in (src, os.path.join(CSRC, "jm_math.h")):
+        with open(path, "rb") as f:
+            h.update(f.read())
+    digest = h.hexdigest()
+    try:
+        with open(out + ".src") as f:
+            fresh = f.read().strip() == digest and os.path.exists(out)
+    except OSError:
+        fresh = False
+    if fresh and not force:
+        return out
+    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
+        raise RuntimeError(f"hipcc not found ({HIPCC}); cannot build {out}")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.check_call([HIPCC, *flags, "-shared", src, "-o", out + ".tmp"])
+    os.replace(out + ".tmp", out)
+    with open(out + ".src", "w") as f:
+        f.write(digest + "\n")
+    return out
+
+
 def build_library(model: CompiledModel, force: bool = False, verbose: bool = False,
                   extra_flags: Optional[List[str]] = None, variant: Optional[int] = None) -> str:
     """Compile the HIP library specialised for `model`'s topology (gfx950)."""
@@ -415,8 +448,7 @@ def build_library(model: CompiledModel, force: bool = False, verbose: bool = Fal
             f"{model.topology_hash()} and no prebuilt {lib} exists")
     # up to five translation units compiled in parallel (the constraint-model kernels are the longest single compiles
     # of a large topology), then linked into one shared library
-    common = [f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
-              f"-DJM_TOPO_HEADER=\"{hdr}\"", "-Wno-unused-value", "-ffp-contract=fast"]
+    common = COMMON_FLAGS + [f"-DJM_TOPO_HEADER=\"{hdr}\""]
     common += list(BUILD_VARIANTS[v])
     common += extra_flags or []
     if qcon_split_min() != 32:

@@ -357,7 +357,8 @@ JM_DEV void sincos_(double x, double * s, double * c)
     const double ck = 1.0 - (0.5 * z - z * pc);
     const int n = (int)fn & 3;
     const double s0 = (n & 1) ? ck : sk, c0 = (n & 1) ? sk : ck;
-    *s = (n & 2) ? -s0 : s0;
+    const double s1 = (n & 2) ? -s0 : s0;
+    *s = x == 0.0 ? x : s1;   // (sin(-0) is -0, but every step above turns -0 into +0: -0 - 0 * c is +0)
     *c = ((n + 1) & 2) ? -c0 : c0;
 }
 #ifdef JM_HOST_EMU
@@ -399,7 +400,8 @@ JM_DEV float rsqrt_(float x) { return 1.0f / ::sqrtf(x); }
 JM_DEV double trunc_(double x) { return ::trunc(x); }
 JM_DEV float trunc_(float x) { return ::truncf(x); }
 // tanh(x) = e / (e + 2), e = expm1(2 |x|) = 2^n (expm1(r) + 1) - 1 with 2|x| = n ln2 + r, |r| <= ln2 / 2 (degree-13
-// Taylor polynomial of expm1, truncation 4e-18 relative); |x| >= 20 saturates.  <= 2 ulp; replaces ocml's
+// Taylor polynomial of expm1, truncation 4e-18 relative); |x| >= 20 saturates.  < 3 ulp (2.8 near x = 0.22: the
+// roundings of e, e + 2 and the quotient add up); replaces ocml's
 // extended-precision tanh (3x the instructions, a dozen coefficients hoisted into VGPRs by LICM).
 JM_DEV double tanh_(double x)
 {
@@ -540,7 +542,7 @@ template<class T> JM_DEV V3<T> log3(const M3<T> & R)
 template<class T> JM_DEV void quat_exp3(V3<T> v, T (&out)[4])
 {
     const T t2 = dot(v, v);
-    const T ts_prec = sizeof(T) == 8 ? T(1.220703125e-4) : T(1.86264515e-2);   // eps^(1/4): TaylorSeriesExpansion::precision<3>()
+    const T ts_prec = Eps<T>::taylor;   // eps^(1/4): TaylorSeriesExpansion::precision<3>()
     T k, w;
     if (t2 > ts_prec)
     {
@@ -570,7 +572,7 @@ template<class T> JM_DEV V3<T> quat_log3(T x, T y, T z, T w, T & theta)
 {
     const T n2 = x * x + y * y + z * z;
     const T n = sqrt_(n2);
-    const T ts_prec = sizeof(T) == 8 ? T(1.220703125e-4) : T(1.86264515e-2);
+    const T ts_prec = Eps<T>::taylor;
     const T sgn = w >= T(0) ? T(1) : T(-1);
     theta = T(2) * atan2_(n, sgn * w);
     const T k = n2 > ts_prec ? sgn * theta / n : sgn * (T(2) / fabs_(w)) * (T(1) - n2 / (T(3) * w * w));
@@ -579,7 +581,7 @@ template<class T> JM_DEV V3<T> quat_log3(T x, T y, T z, T w, T & theta)
 // Jlog3 (Pinocchio v2.7.0 spatial/explog.hpp) applied to a vector: Jlog3(theta, lg) * v
 template<class T> JM_DEV V3<T> jlog3_mul(T theta, V3<T> lg, V3<T> v)
 {
-    const T ts_prec = sizeof(T) == 8 ? T(1.220703125e-4) : T(1.86264515e-2);
+    const T ts_prec = Eps<T>::taylor;
     T alpha, diag;
     if (theta < ts_prec)
     {

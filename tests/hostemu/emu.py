@@ -23,6 +23,12 @@ class EmuIO(C.Structure):
     _fields_ = [("B", C.c_longlong)] + [(n, C.c_void_p) for n in _FIELDS]
 
 
+def host_compiler() -> list:
+    """Compiler and flags of the host builds of the kernel code (also the host twin of tests/device_math)."""
+    return [os.environ.get("EMU_CXX", "g++"), "-O1", *os.environ.get("EMU_EXTRA_FLAGS", "").split(), "-std=c++17", "-fPIC",
+            "-shared", "-march=x86-64-v3", "-ffp-contract=off", "-pthread"]
+
+
 def _lib(model: CompiledModel) -> C.CDLL:
     h = model.topology_hash()
     if h in _CACHE:
@@ -34,9 +40,7 @@ def _lib(model: CompiledModel) -> C.CDLL:
     deps = [os.path.join(_HERE, "emu.cpp"), hdr] + codegen._sources()[1:] + \
            []
     if (not os.path.exists(out)) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.check_call([os.environ.get("EMU_CXX", "g++"), "-O1", *os.environ.get("EMU_EXTRA_FLAGS", "").split(), "-std=c++17", "-fPIC", "-shared", "-march=x86-64-v3",
-                               "-ffp-contract=off", "-pthread", f"-DJM_TOPO_HEADER=\"{hdr}\"",
-                               os.path.join(_HERE, "emu.cpp"), "-o", out])
+        subprocess.check_call(host_compiler() + [f"-DJM_TOPO_HEADER=\"{hdr}\"", os.path.join(_HERE, "emu.cpp"), "-o", out])
     L = C.CDLL(out)
     L.emu_run.argtypes = [C.POINTER(_abi.ModelDesc), C.POINTER(_abi.Options), C.POINTER(EmuIO),
                           C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]

@@ -1,4 +1,5 @@
 // Device math of jm_math.h against the host libm (tools only): sincos_ and tanh_ over log-spaced arguments.
+// The contracts themselves are tested against high-precision values by tests/test_device_math.py.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
