@@ -731,7 +731,26 @@ template<class T, class Tp, int X, class W> JM_DEV void xframe_points(CPtr<T> P,
     p2 = w.oMi[j2].p + w.oMi[j2].R * ld_v3<T>(P, L::XPAR + 8 * X + 1);
 }
 
-// (WC: WorkC, or WorkCA in the instantiation that reads the applied wrenches)
+// Local frame of the rows of a contact point (`pc` in the frame of joint placement `oMi`) and its penetration depth
+// (contact_frame, jm_kernels.h) in the variation instantiation (WorkCA): the height map of the batch arguments at the lane's own
+// patch of it (BatchArgs::ground_off, batch order under the compact launches of the adaptive stepper), flat ground without one.
+// Recomputed where it is used, like the branch-parallel kernels do.  (The plain instantiation keeps its world-aligned rows
+// and a flat ground at compile time, in code of its own: `if constexpr (WC::APPLIED)` at every use.)
+template<class T, class WC> JM_DEV M3<T> con_frame(const WC & w, const SE3<T> & oMi, V3<T> pc, T & depth)
+{
+    const BatchArgs<T> & A = *w.args;
+    V3<T> p1 = oMi.p;
+    if (A.ground_h && A.ground_off)
+    {
+        const long long st = A.lane_map ? A.B_full : A.B;
+        const long long lg = A.lane_map ? (long long)A.lane_map[w.lane] : w.lane;
+        p1.x += A.ground_off[lg];
+        p1.y += A.ground_off[st + lg];
+    }
+    return contact_frame<true>(A, oMi.R, p1, pc, depth);
+}
+
+// (WC: WorkC, or WorkCA in the instantiation that reads the applied wrenches and the height map)
 template<class T, class Tp, class CA, class WC>
 JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd, WC & w, const CA & C,
                              long long lane, long long B, int start_passes)
@@ -806,7 +825,10 @@ JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd,
         constexpr int j = decltype(jc)::value;
         const int r0 = R::NB + 4 * c;
         const V3<T> pc = ld_v3<T>(P, L::CONTACT + 12 * c + 9);
-        const T d = w.oMi[j].p.z + dot(V3<T>{w.oMi[j].R.m20, w.oMi[j].R.m21, w.oMi[j].R.m22}, pc);
+        T d;
+        // (depth against world.groundProfile under the point, engine.cc:3142-3182)
+        if constexpr (WC::APPLIED) (void)con_frame<T>(w, w.oMi[j], pc, d);
+        else d = w.oMi[j].p.z + dot(V3<T>{w.oMi[j].R.m20, w.oMi[j].R.m21, w.oMi[j].R.m22}, pc);
         const bool init = start_passes > 0;
         int32_t f = init ? 1 : flag(R::NB + c);
         if (!refresh)
@@ -932,12 +954,26 @@ JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd,
             {
                 const int d = r - r0;
                 const V3<T> pc = ld_v3<T>(P, L::CONTACT + 12 * c + 9);
+                if constexpr (WC::APPLIED)
+                {
+                    // unit force along t0 / t1 / n or unit torque about n at the contact point, local frame of the ground
+                    // surface (frame_constraint.cc:136-146 with rotationLocal = [t0 t1 n])
+                    T dep_;
+                    const M3<T> Mc = con_frame<T>(w, w.oMi[j], pc, dep_);
+                    const V3<T> col = d == 0 ? V3<T>{Mc.m00, Mc.m01, Mc.m02}
+                                    : d == 1 ? V3<T>{Mc.m10, Mc.m11, Mc.m12} : V3<T>{Mc.m20, Mc.m21, Mc.m22};
+                    if (d < 3) fu = {col, cross(pc, col)};
+                    else fu = {zero3<T>(), col};
+                }
+                else
+                {
                 const M3<T> & Rj = w.oMi[j].R;
                 // unit force (x, y, z) or unit torque about z at the contact point, world aligned
                 const V3<T> col = d == 0 ? V3<T>{Rj.m00, Rj.m01, Rj.m02}
                                 : d == 1 ? V3<T>{Rj.m10, Rj.m11, Rj.m12} : V3<T>{Rj.m20, Rj.m21, Rj.m22};
                 if (d < 3) fu = {col, cross(pc, col)};
                 else fu = {zero3<T>(), col};
+                }
                 jr = j;
                 bmask = R::anc_mask(j);
             }
@@ -1019,8 +1055,20 @@ JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd,
                         if (Tp::contact_joint[c] == j && act.test(R::NB + 4 * c))
                         {
                             const V3<T> pc = ld_v3<T>(P, L::CONTACT + 12 * c + 9);
-                            const V3<T> lin = w.oMi[j].R * (daj.l + cross(daj.a, pc));
-                            const V3<T> ang = w.oMi[j].R * daj.a;
+                            V3<T> lin, ang;
+                            if constexpr (WC::APPLIED)
+                            {
+                                // (rows in the local frame of the ground surface)
+                                T dep_;
+                                const M3<T> Mc = con_frame<T>(w, w.oMi[j], pc, dep_);
+                                lin = Mc * (daj.l + cross(daj.a, pc));
+                                ang = Mc * daj.a;
+                            }
+                            else
+                            {
+                                lin = w.oMi[j].R * (daj.l + cross(daj.a, pc));
+                                ang = w.oMi[j].R * daj.a;
+                            }
                             const int p0 = act.rank(R::NB + 4 * c);
                             ws(R::WA + p0 * NR + pk) = lin.x;
                             ws(R::WA + (p0 + 1) * NR + pk) = lin.y;
@@ -1125,12 +1173,28 @@ JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd,
                 if (act.test(r0))
                 {
                     const V3<T> pc = ld_v3<T>(P, L::CONTACT + 12 * c + 9);
+                    T depth;
+                    V3<T> vlin, vang, alin, aang;
+                    if constexpr (WC::APPLIED)
+                    {
+                        // velocity / drift acceleration in the local frame of the ground surface (LOCAL_WORLD_ALIGNED rotated by
+                        // rotationLocal^T, frame_constraint.cc:151-174; a rotation commutes with the cross product); the
+                        // Baumgarte position term is depth * n, i.e. (0, 0, depth) there
+                        const M3<T> Mc = con_frame<T>(w, w.oMi[j], pc, depth);
+                        vlin = Mc * (w.vel[j].l + cross(w.vel[j].a, pc));
+                        vang = Mc * w.vel[j].a;
+                        alin = Mc * (sa[j].l + cross(sa[j].a, pc));
+                        aang = Mc * sa[j].a;
+                    }
+                    else
+                    {
                     const M3<T> & Rj = w.oMi[j].R;
-                    const T depth = w.oMi[j].p.z + dot(V3<T>{Rj.m20, Rj.m21, Rj.m22}, pc);
-                    const V3<T> vlin = Rj * (w.vel[j].l + cross(w.vel[j].a, pc));
-                    const V3<T> vang = Rj * w.vel[j].a;
-                    V3<T> alin = Rj * (sa[j].l + cross(sa[j].a, pc));
-                    const V3<T> aang = Rj * sa[j].a;
+                    depth = w.oMi[j].p.z + dot(V3<T>{Rj.m20, Rj.m21, Rj.m22}, pc);
+                    vlin = Rj * (w.vel[j].l + cross(w.vel[j].a, pc));
+                    vang = Rj * w.vel[j].a;
+                    alin = Rj * (sa[j].l + cross(sa[j].a, pc));
+                    aang = Rj * sa[j].a;
+                    }
                     alin = alin + cross(vang, vlin);
                     const int p0 = act.rank(r0);
                     ws(R::WB + p0) = -(alin.x + C.kd * vlin.x);
@@ -1329,11 +1393,24 @@ JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd,
                 const V3<T> tW = {T(0), T(0), lam(r0 + 3)};
                 // convertForceGlobalFrameToJoint (utilities/pinocchio.cc:794-809)
                 Sp<T> fl;
+                if constexpr (WC::APPLIED)
+                {
+                    // local components (t0, t1, n; torsion about n): world = rotationLocal lambda (engine.cc:3805-3817)
+                    T dep_;
+                    const M3<T> Mc = con_frame<T>(w, w.oMi[j], fr.p, dep_);
+                    fl.l = tmul(Mc, fW);
+                    fl.a = tmul(Mc, tW) + cross(fr.p, fl.l);
+                    fsum[j] = fsum[j] + fl;
+                    w.cf[c] = {tmul(fr.R, fl.l), tmul(fr.R, tmul(Mc, tW))};
+                }
+                else
+                {
                 fl.l = tmul(w.oMi[j].R, fW);
                 fl.a = tmul(w.oMi[j].R, tW) + cross(fr.p, fl.l);
                 fsum[j] = fsum[j] + fl;
                 // Robot::contactForces_ in the contact frame (engine.cc:3806-3817)
                 w.cf[c] = {tmul(fr.R, fl.l), tmul(fr.R, tmul(w.oMi[j].R, tW))};
+                }
             }
         });
         // user FrameConstraints: force at the frame origin + torque, world aligned, on the frame's parent joint; they act
@@ -1439,10 +1516,23 @@ JM_DEV void constraint_forces_from_multipliers(CPtr<T> P, WC & w, const CA & C, 
             const V3<T> fW = {lam(r0), lam(r0 + 1), lam(r0 + 2)};
             const V3<T> tW = {T(0), T(0), lam(r0 + 3)};
             Sp<T> fl;
+            if constexpr (WC::APPLIED)
+            {
+                // (local components of the ground surface's frame, as in eval_constrained)
+                T dep_;
+                const M3<T> Mc = con_frame<T>(w, w.oMi[j], fr.p, dep_);
+                fl.l = tmul(Mc, fW);
+                fl.a = tmul(Mc, tW) + cross(fr.p, fl.l);
+                w.fext[j] = w.fext[j] + fl;
+                w.cf[c] = {tmul(fr.R, fl.l), tmul(fr.R, tmul(Mc, tW))};
+            }
+            else
+            {
             fl.l = tmul(w.oMi[j].R, fW);
             fl.a = tmul(w.oMi[j].R, tW) + cross(fr.p, fl.l);
             w.fext[j] = w.fext[j] + fl;
             w.cf[c] = {tmul(fr.R, fl.l), tmul(fr.R, tmul(w.oMi[j].R, tW))};
+            }
         }
     });
 }
