@@ -30,6 +30,7 @@
 #include "jm_adaptive.h"
 #include "jm_qdopri.h"
 #include "jm_random.h"
+#include "jm_dispatch.h"
 
 #define JM_ABI_VERSION 9
 
@@ -90,11 +91,11 @@ struct jm_model
     bool root_at_origin = true;  // placement of joint 1 is the identity (limb-parallel kernel)
 };
 
-enum { VARIANT_LANE = 0, VARIANT_QUAD = 1 };
+namespace jd = jm::dispatch;
 
 struct jm_batch
 {
-    int variant = VARIANT_LANE;
+    int variant = jd::FAMILY_LANE;
     const jm_model * model = nullptr;
     long long B = 0;
     int dtype = JM_F64;
@@ -106,23 +107,13 @@ struct jm_batch
     bool qcon_split = true;   // constraint model, large solves: split step launches (JIMINY_AMD_QCON_SPLIT=0 at creation: single kernel)
     bool qcon_split_start = true;   // ... and split start / reset launches (JIMINY_AMD_QCON_SPLIT_START=0: single kernel)
     bool joint_locks = false; // the batch carries user-registered JointConstraints (jm_batch_set_joint_locks)
-    // split stepping of robots whose solve runs one lane per robot (jm_qcon.h, qcon_pgs_lane): the solve kernel counts the
-    // robots it cannot take, its sweeps, its waves and its longest solve on the device (four counters per slot).  A batch
-    // with misses, or whose solves are short (robots standing under control), steps with the single kernel for a while, then one
-    // step in the split form probes again.  The decision for step n only reads the counters of steps <= n - 2 and WAITS for
-    // them (they have long arrived: no stall), and `start` resets the state: the sequence of forms is a function of the
-    // simulated data, not of host timing -- two runs from the same state are bit-identical (reference pin 11)
-    static constexpr int LANE_SLOTS = 4;
-    int32_t * lane_stat = nullptr;        // device, [LANE_SLOTS][4]
-    int32_t * lane_stat_host = nullptr;   // pinned, [LANE_SLOTS][4]
-    hipEvent_t lane_ev[LANE_SLOTS] = {};
-    long long lane_step_of[LANE_SLOTS] = {-1, -1, -1, -1};   // step whose counters the slot is waiting for (-1: free)
-    long long lane_step = 0;              // split-capable step launches since `start`
-    int split_cooldown = 0;
-    int split_chunks = 1;     // ... as this many independent chunks on streams of their own (JIMINY_AMD_QCON_SPLIT_CHUNKS; measured: no gain)
-    hipStream_t split_stream[8] = {};
-    hipEvent_t split_fork = nullptr, split_join[8] = {};
-    bool split_streams_made = false;
+    // split stepping of robots whose solve runs one lane per robot (jm_qcon.h, qcon_pgs_lane): that kernel counts into one of four
+    // slots, the history turns the counters of steps <= n - 2 into the form of step n (jm_dispatch.h); made by jm_batch_create
+    jd::SplitHistory history;
+    int32_t * lane_stat = nullptr;        // device, [SLOTS][4]
+    int32_t * lane_stat_host = nullptr;   // pinned, [SLOTS][4]
+    hipEvent_t lane_ev[jd::SplitHistory::SLOTS] = {};
+    bool debug_split = false, split_capture = false;   // JM_DEBUG_SPLIT (print the counters as they are absorbed), JIMINY_AMD_QCON_SPLIT_CAPTURE (a captured step may take the split form) at creation
     // adaptive stepper: caller-owned workspace / per-lane state, library-owned active-lane counter
     void * ad_ws = nullptr;
     double * ad_fs = nullptr;
@@ -173,7 +164,7 @@ int32_t upload_params(jm_batch * b)
 template<class Tp> int32_t constraint_ws_rows_of(const jm_batch * b)
 {
     if constexpr (Tp::QUAD)
-        if (b->variant == VARIANT_QUAD)
+        if (b->variant == jd::FAMILY_QUAD)
         {
             int rows = jm::qcon_ws_rows<double, Tp>();
             if constexpr (jm::qcon_split<Tp>())
@@ -223,314 +214,198 @@ template<class T> jm::BatchArgs<T> make_args(const jm_batch * b)
     return A;
 }
 
-// limb-parallel kernel (4 lanes per robot): only instantiated for topologies that have the structure
-template<class T, class Tp> void launch_quad(jm_batch * b, jm::BatchArgs<T> & A, hipStream_t s)
+template<class T, class Tp> constexpr jd::Traits traits_of()
 {
-    if constexpr (Tp::QUAD)
+    if constexpr (Tp::QUAD) return {true, jm::qcon_split<Tp>(), jm::qcon_split_large<Tp>(), jm::quad_block_waves<T, Tp>(), jm::qcon_split_lane<Tp>()};
+    else return {false, false, false, 1, false};
+}
+
+// run-time facts of a launch (jm_dispatch.h) but for the stream's capture state and the verdict of the history
+template<class T> jd::Facts facts_of(const jm_batch * b, const jm::BatchArgs<T> & A)
+{
+    jd::Facts f = {};
+    f.mode = A.mode; f.f64 = std::is_same<T, double>::value; f.family = b->variant;
+    f.constraint = b->copt.contact_model == JM_CONTACT_CONSTRAINT; f.con_rows = jm::ConRows<Topo>::NR > 0;
+    f.model_lane = A.model_lane; f.ground = A.ground_h; f.applied = A.applied; f.friction = A.friction;
+    f.joint_locks = b->joint_locks; f.compact = b->ov_flags; f.B = A.B; f.n_cus = b->n_cus;
+    f.torsion = b->copt.torsion >= 2.220446049250313e-16;   // (four-row contact blocks: never the fixed layout)
+    f.split = b->qcon_split; f.split_start = b->qcon_split_start; f.split_capture = b->split_capture;
+    return f;
+}
+
+// the history once it has taken in the counters of the steps <= n - 2 that are still out (long arrived: no stall)
+const jd::SplitHistory & drained_history(jm_batch * b)
+{
+    for (int k = b->history.due(); k >= 0; k = b->history.due())
     {
-        constexpr int nth = 64 * jm::quad_block_waves<T, Tp>();  // 4 lanes per robot
-        const unsigned grid = (unsigned)((A.B + nth / 4 - 1) / (nth / 4));  // A.B <= b->B (compact adaptive batches)
-        if constexpr (std::is_same<T, double>::value)
-        {
-            if (A.model_lane || A.ground_h || A.applied || A.friction)
-            {
-                hipLaunchKernelGGL((jm::k_quad_gen<T, Tp>), dim3(grid), dim3(nth), 0, s, A);
-                return;
-            }
-        }
-        // small batch: one wave per block so that the waves spread over all the CUs (the per-block limb table is
-        // a few kB, staging it four times as often is noise next to idle CUs)
-        if constexpr (jm::quad_block_waves<T, Tp>() > 1)
-        {
-            if ((long long)grid < 2LL * b->n_cus)
-            {
-                const unsigned grid1 = (unsigned)((A.B + 15) / 16);
-                hipLaunchKernelGGL((jm::k_quad<T, Tp, 1>), dim3(grid1), dim3(64), 0, s, A);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((jm::k_quad<T, Tp>), dim3(grid), dim3(nth), 0, s, A);
+        (void)hipEventSynchronize(b->lane_ev[k]);
+        const int32_t * st = b->lane_stat_host + 4 * k;
+        if (b->debug_split) std::fprintf(stderr, "[split] miss %d sweeps %d waves %d longest %d\n", st[0], st[1], st[2], st[3]);
+        b->history.absorb(k, st);
     }
-    else { (void)b; (void)A; (void)s; }
+    return b->history;
 }
 
-// streams / events of the chunked split stepping, made on first use (non-blocking streams: no implicit ordering with the
-// legacy default stream; the fork / join events order them with the caller's stream)
-bool split_streams(jm_batch * b)
+// constraint contact model on the branch-parallel decomposition (jm_qcon.h): its arguments from those of the lane family
+jm::QConArgs<double> qcon_args(const jm::BatchArgs<double> & A, const jm::ConArgs<double> & C0)
 {
-    if (b->split_streams_made) return true;
-    if (hipEventCreateWithFlags(&b->split_fork, hipEventDisableTiming) != hipSuccess) return false;
-    for (int c = 0; c < b->split_chunks; ++c)
-        if (hipStreamCreateWithFlags(&b->split_stream[c], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&b->split_join[c], hipEventDisableTiming) != hipSuccess)
-            return false;
-    b->split_streams_made = true;
-    return true;
+    jm::QConArgs<double> C;
+    C.flags = C0.flags; C.data = C0.data; C.ws = C0.ws; C.friction = C0.friction;
+    C.kp = C0.kp; C.kd = C0.kd; C.kp_lock = C0.kp_lock; C.kd_lock = C0.kd_lock; C.torsion = C0.torsion; C.reg = C0.reg; C.tol_abs = C0.tol_abs; C.tol_rel = C0.tol_rel;
+    C.iter_max = C0.iter_max; C.ground_h = A.ground_h; C.ground_nx = A.ground_nx; C.ground_ny = A.ground_ny;
+    C.ground_x0 = A.ground_x0; C.ground_y0 = A.ground_y0; C.ground_dx = A.ground_dx; C.ground_dy = A.ground_dy;
+    C.stage = nullptr; C.split_e = 0; C.split_pass = 0; C.split_r0 = 0; C.split_r1 = (int)A.B;
+    return C;
 }
 
-// constraint contact model on the branch-parallel decomposition (jm_qcon.h)
-template<class Tp> void launch_quad_con(jm_batch * b, jm::BatchArgs<double> & A, const jm::ConArgs<double> & C0, hipStream_t s)
+// streamed solve of the split forms: solves of up to 64 rows, then the waves that hold a larger one, then the waves whose
+// robots all have few active joint rows (operational-space form, jm_qtip.h)
+template<class Tp> void qcon_split_solve(const jm::BatchArgs<double> & A, const jm::QConArgs<double> & C, unsigned g64, hipStream_t s)
 {
-    if constexpr (Tp::QUAD)
+    hipLaunchKernelGGL((jm::k_qcon_pgs<double, Tp, 8, 0, JM_QCON_PGS_DEPTH>), dim3(g64), dim3(256), 0, s, C, A.P, (unsigned)A.B);
+    if constexpr (jm::QConRows<Tp>::MAXM > 64)
+        hipLaunchKernelGGL((jm::k_qcon_pgs<double, Tp, 12, 64, JM_QCON_PGS_DEPTH - 1>), dim3(g64), dim3(256), 0, s, C, A.P, (unsigned)A.B);
+    if constexpr (jm::QTip<Tp>::ON)
+        hipLaunchKernelGGL((jm::k_qtip_pgs<double, Tp>), dim3(g64), dim3(256), 0, s, C, A.P, (unsigned)A.B);
+}
+
+// Engine::start / reset as launches of the split kernels, the four passes of the initialisation (engine.cc:1399-1467): first
+// pass (every constraint enabled, hysteresis, free acceleration with u = 0, matrix and right-hand side) | exact solve | three
+// times (multipliers -> u, free acceleration, right-hand side | Gauss-Seidel) | closing evaluation with the outputs.  (The
+// single kernel took 52-67 ms per launch at B = 32 768 whatever the number of lanes that restart: NOTES/LAB_NOTEBOOK.md.)
+template<class Tp> void launch_split_start(const jm::BatchArgs<double> & A, jm::QConArgs<double> C, hipStream_t s)
+{
+    C.stage = C.ws + (size_t)jm::qcon_split_region_rows<double, Tp>() * (size_t)A.B;
+    const unsigned g64 = (unsigned)((A.B + 63) / 64);
+    hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 1, 1>), dim3(g64), dim3(256), 0, s, A, C);
+    hipLaunchKernelGGL((jm::k_qcon_exact<double, Tp>), dim3(g64), dim3(256), 0, s, C);
+    if constexpr (jm::QTip<Tp>::ON)
+        hipLaunchKernelGGL((jm::k_qtip_exact<double, Tp>), dim3((unsigned)((A.B + 255) / 256)), dim3(256), 0, s, C);
+    for (int pass = 1; pass <= 3; ++pass)
     {
-        jm::QConArgs<double> C;
-        C.flags = C0.flags; C.data = C0.data; C.ws = C0.ws; C.friction = C0.friction;
-        C.kp = C0.kp; C.kd = C0.kd; C.kp_lock = C0.kp_lock; C.kd_lock = C0.kd_lock; C.torsion = C0.torsion; C.reg = C0.reg; C.tol_abs = C0.tol_abs; C.tol_rel = C0.tol_rel;
-        C.iter_max = C0.iter_max;
-        C.ground_h = A.ground_h; C.ground_nx = A.ground_nx; C.ground_ny = A.ground_ny;
-        C.ground_x0 = A.ground_x0; C.ground_y0 = A.ground_y0; C.ground_dx = A.ground_dx; C.ground_dy = A.ground_dy;
-        C.stage = nullptr; C.split_e = 0; C.split_pass = 0; C.split_r0 = 0; C.split_r1 = (int)A.B;
-        constexpr int nth = 64 * jm::qcon_block_waves<double, Tp>();
-        const unsigned grid = (unsigned)((A.B + nth / 4 - 1) / (nth / 4));
-        if constexpr (jm::qcon_split<Tp>())
-        {
-            // Engine::start / reset of such robots: the four passes of the initialisation (engine.cc:1399-1467) as launches
-            // of the split kernels -- first pass (every constraint enabled, hysteresis, free acceleration with u = 0, matrix
-            // and right-hand side) | exact solve | three times (multipliers -> u, free acceleration, right-hand side |
-            // Gauss-Seidel) | closing evaluation with the outputs.  The single kernel (k_quad_con: 2064 spilled VGPRs, 137 kB
-            // of LDS for stage rows a start does not need, the general Gauss-Seidel form at one row per memory round trip)
-            // took 52-67 ms per launch at B = 32 768 whatever the number of lanes that restart.
-            if (b->qcon_split && (A.mode == jm::MODE_START || A.mode == jm::MODE_RESET) && !(A.model_lane || A.applied || A.ground_h) &&
-                (A.B & 15) == 0 && !b->ov_flags && b->qcon_split_start)
-            {
-                C.stage = C.ws + (size_t)jm::qcon_split_region_rows<double, Tp>() * (size_t)A.B;
-                const unsigned g64 = (unsigned)((A.B + 63) / 64);
-                auto solve = [&]() {
-                    hipLaunchKernelGGL((jm::k_qcon_pgs<double, Tp, 8, 0, JM_QCON_PGS_DEPTH>), dim3(g64), dim3(256), 0, s, C, A.P, (unsigned)A.B);
-                    if constexpr (jm::QConRows<Tp>::MAXM > 64)
-                        hipLaunchKernelGGL((jm::k_qcon_pgs<double, Tp, 12, 64, JM_QCON_PGS_DEPTH - 1>), dim3(g64), dim3(256), 0, s, C, A.P, (unsigned)A.B);
-                    if constexpr (jm::QTip<Tp>::ON)
-                        hipLaunchKernelGGL((jm::k_qtip_pgs<double, Tp>), dim3(g64), dim3(256), 0, s, C, A.P, (unsigned)A.B);
-                };
-                C.split_pass = 0;
-                hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 1, 1>), dim3(g64), dim3(256), 0, s, A, C);
-                hipLaunchKernelGGL((jm::k_qcon_exact<double, Tp>), dim3(g64), dim3(256), 0, s, C);
-                if constexpr (jm::QTip<Tp>::ON)
-                    hipLaunchKernelGGL((jm::k_qtip_exact<double, Tp>), dim3((unsigned)((A.B + 255) / 256)), dim3(256), 0, s, C);
-                for (int pass = 1; pass <= 3; ++pass)
-                {
-                    C.split_pass = pass;
-                    hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 1, 1>), dim3(g64), dim3(256), 0, s, A, C);
-                    solve();
-                }
-                C.split_pass = 4;
-                hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 2, 1>), dim3(g64), dim3(256), 0, s, A, C);
-                return;
-            }
-            // robots whose solves live in the workspace: step launches go through pre | solve | post per evaluation (jm_qcon.h)
-            // robots with small solves (one lane per robot): only while every solve of the batch fits that form -- a robot
-            // that does not (more active bounds than the layout holds, torsion rows, a joint lock) falls to the streamed form,
-            // an order of magnitude slower per robot, and the split form only pays off for long solves: the counters of the solve
-            // kernel decide (see jm_batch::lane_stat).
-            bool lane_ok = true;
-            hipStreamCaptureStatus cap0 = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(s, &cap0) == hipSuccess && cap0 != hipStreamCaptureStatusNone;
-            if constexpr (!jm::qcon_split_large<Tp>())
-            {
-                if (A.mode == jm::MODE_START)
-                {
-                    // a simulation starts in the split form with a clean history: the forms of its steps depend on its data only
-                    b->lane_step = 0;
-                    b->split_cooldown = 0;
-                    for (int i = 0; i < jm_batch::LANE_SLOTS; ++i) b->lane_step_of[i] = -1;
-                }
-                if (A.mode == jm::MODE_STEP && !capturing)
-                {
-                    for (int pass = 0; pass < jm_batch::LANE_SLOTS; ++pass)
-                    {
-                        // oldest outstanding slot of a step <= n - 2
-                        int k = -1;
-                        for (int i = 0; i < jm_batch::LANE_SLOTS; ++i)
-                            if (b->lane_step_of[i] >= 0 && b->lane_step_of[i] <= b->lane_step - 2 && (k < 0 || b->lane_step_of[i] < b->lane_step_of[k])) k = i;
-                        if (k < 0) break;
-                        (void)hipEventSynchronize(b->lane_ev[k]);
-                        b->lane_step_of[k] = -1;
-                        const int32_t * st = b->lane_stat_host + 4 * k;   // [0] misfits, [1] sweeps, [2] waves, [3] longest solve
-                        if (std::getenv("JM_DEBUG_SPLIT")) std::fprintf(stderr, "[split] miss %d sweeps %d waves %d longest %d\n", st[0], st[1], st[2], st[3]);
-                        int cool = 0;
-                        if (st[0] > 0) cool = 64;
-                        // measured on ANYmal, 65 536 robots, per evaluation: single kernel ~147 us + 5.3 us per average sweep (its
-                        // waves queue four deep on a SIMD); split form ~247 us + 1.55 us per sweep of the LONGEST solve of the launch
-                        // (every wave of the solve kernel is resident at once)
-                        else if (st[2] > 0 && 5.3 * (double)st[1] / (double)st[2] - 1.55 * (double)st[3] < 100.0) cool = 256;
-                        if (cool > b->split_cooldown) b->split_cooldown = cool;
-                    }
-                    if (b->split_cooldown > 0) { --b->split_cooldown; lane_ok = false; }
-                    ++b->lane_step;
-                }
-                // (a captured step keeps one form for all its replays: the single kernel, which is never far off)
-                if (capturing && !std::getenv("JIMINY_AMD_QCON_SPLIT_CAPTURE")) lane_ok = false;
-                if (C0.torsion >= 2.220446049250313e-16) lane_ok = false;   // (four-row contact blocks: never the fixed layout)
-            }
-            if (lane_ok && b->qcon_split && A.mode == jm::MODE_STEP && !(A.model_lane || A.applied || A.ground_h) && (A.B & 15) == 0 && !b->ov_flags)
-            {
-                int32_t * miss = nullptr;
-                int lane_slot = -1;
-                if constexpr (!jm::qcon_split_large<Tp>())
-                    if (!capturing)
-                    {
-                        if (!b->lane_stat)
-                        {
-                            bool ok = hipMalloc((void **)&b->lane_stat, 4 * jm_batch::LANE_SLOTS * sizeof(int32_t)) == hipSuccess &&
-                                      hipHostMalloc((void **)&b->lane_stat_host, 4 * jm_batch::LANE_SLOTS * sizeof(int32_t), hipHostMallocDefault) == hipSuccess;
-                            for (int i = 0; ok && i < jm_batch::LANE_SLOTS; ++i) ok = hipEventCreateWithFlags(&b->lane_ev[i], hipEventDisableTiming) == hipSuccess;
-                            if (!ok) b->lane_stat = nullptr;
-                            else std::memset(b->lane_stat_host, 0, 4 * jm_batch::LANE_SLOTS * sizeof(int32_t));
-                        }
-                        if (b->lane_stat)
-                        {
-                            lane_slot = (int)((b->lane_step - 1) % jm_batch::LANE_SLOTS);   // (drained above: its step is <= n - 4)
-                            miss = b->lane_stat + 4 * lane_slot;
-                            (void)hipMemsetAsync(miss, 0, 4 * sizeof(int32_t), s);
-                        }
-                    }
-                C.stage = C.ws + (size_t)jm::qcon_split_region_rows<double, Tp>() * (size_t)A.B;
-                const int pre = A.command_changed ? 1 : 0;
-                const int n_evals = pre + A.n_sub * (A.solver == JM_SOLVER_RUNGE_KUTTA_4 ? 4 : 1);
-                // The solve launch lasts as long as its slowest robot (a few of 32 768 run into the iteration cap) while
-                // most of the chip idles.  Option (JIMINY_AMD_QCON_SPLIT_CHUNKS = n > 1, off by default): the batch steps as n
-                // independent chunks, each through its own chain of launches on a stream of its own, so that the tail of one
-                // chunk could overlap the work of the others.  Measured on the MI355X (Atlas, B = 32 768): 9.2 ms per launch
-                // with one chain, 8.8 with two chunks, 12.2 with four, 15.9 with eight -- the chains mostly serialise.
-                // (Never while the caller's stream is being captured into a graph.)
-                int n_chunks = 1;
-                hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-                if (b->split_chunks > 1 && A.B >= 64LL * 8 * b->split_chunks && hipStreamIsCapturing(s, &cap) == hipSuccess &&
-                    cap == hipStreamCaptureStatusNone && split_streams(b))
-                    n_chunks = b->split_chunks;
-                const long long per = (((A.B + n_chunks - 1) / n_chunks) + 63) / 64 * 64;
-                if (n_chunks > 1)
-                {
-                    hipEventRecord(b->split_fork, s);
-                    for (int c = 0; c < n_chunks; ++c) hipStreamWaitEvent(b->split_stream[c], b->split_fork, 0);
-                }
-                for (int c = 0; c < n_chunks; ++c)
-                {
-                    const hipStream_t sc = n_chunks > 1 ? b->split_stream[c] : s;
-                    C.split_r0 = (int)(c * per);
-                    C.split_r1 = (int)((c + 1) * per < A.B ? (c + 1) * per : A.B);
-                    if (C.split_r1 <= C.split_r0) continue;
-                    const unsigned g64 = (unsigned)((C.split_r1 - C.split_r0 + 63) / 64);
-                    for (int e = 0; e < n_evals; ++e)
-                    {
-                        C.split_e = e;
-                        hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 1, 0>), dim3(g64), dim3(256), 0, sc, A, C);
-                        // (robots whose system fits the fixed 16-row layout: one lane per robot, out of registers -- jm_qcon.h,
-                        // qcon_pgs_lane; they are marked done for the streamed form that follows)
-                        if constexpr (jm::QLanePgs<Tp>::FITS && JM_QCON_PGS_LANE)
-                            hipLaunchKernelGGL((jm::k_qcon_pgs_lane<double, Tp>), dim3((unsigned)((C.split_r1 - C.split_r0 + 63) / 64)), dim3(64), 0, sc, C, A.P, miss);
-                        // (solves of up to 64 rows, then the waves that hold a larger one)
-                        hipLaunchKernelGGL((jm::k_qcon_pgs<double, Tp, 8, 0, JM_QCON_PGS_DEPTH>), dim3(g64), dim3(256), 0, sc, C, A.P, (unsigned)A.B);
-                        if constexpr (jm::QConRows<Tp>::MAXM > 64)
-                            hipLaunchKernelGGL((jm::k_qcon_pgs<double, Tp, 12, 64, JM_QCON_PGS_DEPTH - 1>), dim3(g64), dim3(256), 0, sc, C, A.P, (unsigned)A.B);
-                        // (the waves whose robots all have few active joint rows: operational-space form, jm_qtip.h)
-                        if constexpr (jm::QTip<Tp>::ON)
-                            hipLaunchKernelGGL((jm::k_qtip_pgs<double, Tp>), dim3(g64), dim3(256), 0, sc, C, A.P, (unsigned)A.B);
-                        hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 2, 0>), dim3(g64), dim3(256), 0, sc, A, C);
-                    }
-                }
-                if (n_chunks > 1)
-                    for (int c = 0; c < n_chunks; ++c)
-                    {
-                        hipEventRecord(b->split_join[c], b->split_stream[c]);
-                        hipStreamWaitEvent(s, b->split_join[c], 0);
-                    }
-                if (miss)
-                {
-                    (void)hipMemcpyAsync(b->lane_stat_host + 4 * lane_slot, miss, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                    (void)hipEventRecord(b->lane_ev[lane_slot], s);
-                    b->lane_step_of[lane_slot] = b->lane_step - 1;
-                }
-                return;
-            }
-        }
-        // (user-registered JointConstraints: kernels built with them -- the variation kernel, or any kernel of a split topology)
-        // (`start` / `reset` -- Engine::start's four passes with the exact solve -- are instantiations of their own)
-        const bool init = A.mode == jm::MODE_START || A.mode == jm::MODE_RESET;
-        if (A.model_lane || A.applied || A.ground_h || (b->joint_locks && !jm::qcon_split<Tp>()))
-        {
-            if (init) hipLaunchKernelGGL((jm::k_quad_con_gen<double, Tp, 1>), dim3(grid), dim3(nth), 0, s, A, C);
-            else hipLaunchKernelGGL((jm::k_quad_con_gen<double, Tp, 0>), dim3(grid), dim3(nth), 0, s, A, C);
-        }
-        else if (init) hipLaunchKernelGGL((jm::k_quad_con<double, Tp, 1>), dim3(grid), dim3(nth), 0, s, A, C);
-        else hipLaunchKernelGGL((jm::k_quad_con<double, Tp, 0>), dim3(grid), dim3(nth), 0, s, A, C);
+        C.split_pass = pass;
+        hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 1, 1>), dim3(g64), dim3(256), 0, s, A, C);
+        qcon_split_solve<Tp>(A, C, g64, s);
     }
-    else { (void)b; (void)A; (void)C0; (void)s; }
+    C.split_pass = 4;
+    hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 2, 1>), dim3(g64), dim3(256), 0, s, A, C);
 }
 
+// step launches of the split form: pre | solve | post per evaluation (jm_qcon.h).  Robots whose system fits the fixed 16-row
+// layout solve one lane per robot, out of registers (qcon_pgs_lane), and are marked done for the streamed form that follows;
+// with `counters` that kernel counts into the history's slot of this step, read back behind the chain.
+template<class Tp> void launch_split_step(jm_batch * b, const jm::BatchArgs<double> & A, jm::QConArgs<double> C, bool counters, hipStream_t s)
+{
+    const int slot = b->history.slot();
+    int32_t * miss = counters ? b->lane_stat + 4 * slot : nullptr;
+    if (miss) (void)hipMemsetAsync(miss, 0, 4 * sizeof(int32_t), s);
+    C.stage = C.ws + (size_t)jm::qcon_split_region_rows<double, Tp>() * (size_t)A.B;
+    const int n_evals = (A.command_changed ? 1 : 0) + A.n_sub * (A.solver == JM_SOLVER_RUNGE_KUTTA_4 ? 4 : 1);
+    const unsigned g64 = (unsigned)((A.B + 63) / 64);
+    for (int e = 0; e < n_evals; ++e)
+    {
+        C.split_e = e;
+        hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 1, 0>), dim3(g64), dim3(256), 0, s, A, C);
+        if constexpr (jm::qcon_split_lane<Tp>())
+            hipLaunchKernelGGL((jm::k_qcon_pgs_lane<double, Tp>), dim3(g64), dim3(64), 0, s, C, A.P, miss);
+        qcon_split_solve<Tp>(A, C, g64, s);
+        hipLaunchKernelGGL((jm::k_quad_con_split<double, Tp, 2, 0>), dim3(g64), dim3(256), 0, s, A, C);
+    }
+    if (miss)
+    {
+        (void)hipMemcpyAsync(b->lane_stat_host + 4 * slot, miss, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        (void)hipEventRecord(b->lane_ev[slot], s);
+        b->history.recorded(slot);
+    }
+}
+
+jm::ConArgs<double> con_args(const jm_batch * b)
+{
+    jm::ConArgs<double> C;
+    C.flags = b->ov_flags ? b->ov_flags : (int32_t *)b->field[JM_F_CON_FLAGS];
+    C.data = (double *)(b->ov_data ? b->ov_data : b->field[JM_F_CON_DATA]);
+    C.ws = (double *)(b->ov_ws ? b->ov_ws : b->field[JM_F_WORKSPACE]);
+    // per-lane friction: bound field (compact batches of the adaptive stepper read it through BatchArgs::lane_map)
+    C.friction = (const double *)b->field[JM_F_FRICTION];
+    const double omega = 2.0 * 3.14159265358979323846 * b->copt.stabilization_freq;  // abstract_constraint.cc:88-98
+    C.kp = omega * omega; C.kd = 2.0 * omega;
+    // user-registered constraints: gains of their own when the option says so (jm_constraint_options, ABI 6)
+    const double omega_u = 2.0 * 3.14159265358979323846 * b->copt.user_stabilization_freq;
+    C.kp_lock = b->copt.user_stabilization_freq < 0.0 ? C.kp : omega_u * omega_u;
+    C.kd_lock = b->copt.user_stabilization_freq < 0.0 ? C.kd : 2.0 * omega_u;
+    C.torsion = b->copt.torsion; C.reg = b->copt.regularization;
+    C.tol_abs = b->copt.tol_abs; C.tol_rel = b->copt.tol_rel; C.iter_max = b->copt.pgs_iter_max;
+    C.xl = nullptr; C.xstride = 0; C.yl = nullptr; C.ystride = 0; C.yrows = 0;  // set by the kernel (LDS)
+    C.park = nullptr; C.park_rows = 0;
+    return C;
+}
+
+// the kernels of a form; false when this topology has none (the `if constexpr` guards keep a topology from instantiating
+// kernels it has no use for: a form whose guard is off is a defect of the selector, never a silent no-op).  The kernels are
+// named in the order the compiler has always met them: the register allocation of some follows it
+template<class T, class Tp> bool launch_form(jm_batch * b, const jm::BatchArgs<T> & A, const jd::Selection & sel, hipStream_t s)
+{
+    constexpr bool F64 = std::is_same<T, double>::value, SPLIT = traits_of<T, Tp>().qcon_split;
+    constexpr int waves = traits_of<T, Tp>().block_waves;   // (the branch-parallel kernels: 4 lanes per robot)
+    const dim3 grid((unsigned)((A.B + 63) / 64)), qgrid((unsigned)((A.B + 16 * waves - 1) / (16 * waves))), grid1((unsigned)((A.B + 15) / 16));
+    // the constraint model.  Its single kernel on the branch-parallel decomposition: `start` / `reset` -- Engine::start's four
+    // passes with the exact solve -- and the variation form (user JointConstraints too, unless the topology splits) are
+    // instantiations of their own
+    if constexpr (F64)
+    {
+        constexpr int cw = [] { if constexpr (Tp::QUAD) return jm::qcon_block_waves<double, Tp>(); else return 1; }();
+        const dim3 cgrid((unsigned)((A.B + 16 * cw - 1) / (16 * cw)));
+        const jm::ConArgs<double> C = con_args(b);
+        const jm::QConArgs<double> Q = qcon_args(A, C);
+        switch (sel.form)
+        {
+        case jd::SPLIT_START: if constexpr (SPLIT) launch_split_start<Tp>(A, Q, s); return SPLIT;
+        case jd::SPLIT_STEP: case jd::SPLIT_STEP_LANE: if constexpr (SPLIT) launch_split_step<Tp>(b, A, Q, sel.counters, s); return SPLIT;
+        case jd::QCON_GEN_INIT: if constexpr (Tp::QUAD) hipLaunchKernelGGL((jm::k_quad_con_gen<double, Tp, 1>), cgrid, dim3(64 * cw), 0, s, A, Q); return Tp::QUAD;
+        case jd::QCON_GEN: if constexpr (Tp::QUAD) hipLaunchKernelGGL((jm::k_quad_con_gen<double, Tp, 0>), cgrid, dim3(64 * cw), 0, s, A, Q); return Tp::QUAD;
+        case jd::QCON_INIT: if constexpr (Tp::QUAD) hipLaunchKernelGGL((jm::k_quad_con<double, Tp, 1>), cgrid, dim3(64 * cw), 0, s, A, Q); return Tp::QUAD;
+        case jd::QCON: if constexpr (Tp::QUAD) hipLaunchKernelGGL((jm::k_quad_con<double, Tp, 0>), cgrid, dim3(64 * cw), 0, s, A, Q); return Tp::QUAD;
+        case jd::LANE_CON_GEN: if constexpr (!Tp::QUAD) hipLaunchKernelGGL((jm::k_constrained<double, Tp, true>), grid, dim3(64), 0, s, A, C); return !Tp::QUAD;
+        case jd::LANE_CON: hipLaunchKernelGGL((jm::k_constrained<double, Tp, false>), grid, dim3(64), 0, s, A, C); return true;
+        default: break;
+        }
+    }
+    switch (sel.form)
+    {
+    case jd::QUAD_GEN: if constexpr (Tp::QUAD && F64) hipLaunchKernelGGL((jm::k_quad_gen<T, Tp>), qgrid, dim3(64 * waves), 0, s, A); return Tp::QUAD && F64;
+    case jd::QUAD_ONE_WAVE: if constexpr (Tp::QUAD && waves > 1) hipLaunchKernelGGL((jm::k_quad<T, Tp, 1>), grid1, dim3(64), 0, s, A); return Tp::QUAD && waves > 1;
+    case jd::QUAD: if constexpr (Tp::QUAD) hipLaunchKernelGGL((jm::k_quad<T, Tp>), qgrid, dim3(64 * waves), 0, s, A); return Tp::QUAD;
+    case jd::LANE_BATCH_GEN: if constexpr (F64 && !Tp::QUAD) hipLaunchKernelGGL((jm::k_batch<T, Tp, true>), grid, dim3(64), 0, s, A); return F64 && !Tp::QUAD;
+    case jd::LANE_BATCH: hipLaunchKernelGGL((jm::k_batch<T, Tp, false>), grid, dim3(64), 0, s, A); return true;
+    default: return false;
+    }
+}
+
+// every launch of the model kernels: facts -> form (jm_dispatch.h) -> the kernels of that form
 template<class T> int32_t launch(jm_batch * b, jm::BatchArgs<T> & A, void * stream)
 {
     HIP_TRY(hipSetDevice(b->device));
     const hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((A.B + 63) / 64);
+    constexpr jd::Traits traits = traits_of<T, Topo>();
+    jd::Facts f = facts_of<T>(b, A);
+    // a simulation starts with a clean history: the forms of its steps depend on its data only
+    if (A.mode == jm::MODE_START) b->history.reset();
+    // a constraint step whose form the history chooses; a captured one neither reads nor advances it
+    const bool lane_step = traits.lane_history() && f.f64 && f.constraint && f.con_rows && f.family == jd::FAMILY_QUAD && A.mode == jm::MODE_STEP;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    f.capturing = lane_step && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    const bool stepping = lane_step && !f.capturing;
+    if (stepping) f.cooling = !drained_history(b).allowed();
+    const jd::Selection sel = jd::select_form(traits, f);
+    if (sel.form == jd::REFUSED) return fail(JM_ENOTIMPL, sel.refusal);
+    if (f.constraint && f.con_rows && (!b->field[JM_F_CON_FLAGS] || !b->field[JM_F_CON_DATA] || !b->field[JM_F_WORKSPACE]))
+        return fail(JM_ECONTROLFLOW, "contacts.model = 'constraint': the con_flags, con_data and workspace fields must be bound");
+    if (stepping) (void)b->history.take_step();
     // only the step launches are timed: the roofline leg prices one pass of the hot path, not the
     // (cheaper, single-evaluation) start / reset / dynamics launches
-    {
-        // body parameters per lane and height maps: the variation form of the branch-parallel kernels only; friction per lane and
-        // applied wrenches: that form (float64) or the one-robot-per-lane kernels, which read them as they are (ABI 9)
-        const bool quad = Topo::QUAD && b->variant == VARIANT_QUAD;
-        // (height-map ground on the one-robot-per-lane kernels: their variation instantiation, under either contact model --
-        // with the constraint model the contact rows live in the local frame of the surface, jm_constraint.h)
-        if (A.ground_h && !(std::is_same<T, double>::value && (quad || !Topo::QUAD)))
-            return fail(JM_ENOTIMPL, "a height-map ground needs a float64 batch (and, on a branch-parallel topology, its own kernels)");
-        if (A.model_lane && !(std::is_same<T, double>::value && (quad || !Topo::QUAD)))
-            return fail(JM_ENOTIMPL, "per-lane body parameters need a float64 batch (and, on a branch-parallel topology, its own kernels)");
-        if (A.friction && quad && !std::is_same<T, double>::value)
-            return fail(JM_ENOTIMPL, "per-lane friction on a branch-parallel topology needs a float64 batch");
-        // (applied wrenches: an instantiation of their own in either family; the one-robot-per-lane one exists for the
-        // topologies that have no branch-parallel kernels)
-        if (A.applied && !(std::is_same<T, double>::value && (quad || !Topo::QUAD)))
-            return fail(JM_ENOTIMPL, "applied wrenches need a float64 batch (and, on a branch-parallel topology, its own kernels)");
-    }
     const bool timed = b->timing && A.mode == jm::MODE_STEP && b->n_timed < JM_TIMING_RING;
     if (timed) HIP_TRY(hipEventRecord(b->ev[2 * b->n_timed], s));
-    if (b->copt.contact_model == JM_CONTACT_CONSTRAINT)
-    {
-        // float64 only: the reference's precision; its PGS tolerances (1e-5 absolute on residual
-        // differences) are below float32 round-off of the delassus products
-        if constexpr (std::is_same<T, double>::value)
-        {
-            using R = jm::ConRows<Topo>;
-            if (R::NR > 0 && (!b->field[JM_F_CON_FLAGS] || !b->field[JM_F_CON_DATA] || !b->field[JM_F_WORKSPACE]))
-                return fail(JM_ECONTROLFLOW, "contacts.model = 'constraint': the con_flags, con_data and workspace fields must be bound");
-            jm::ConArgs<T> C;
-            C.flags = b->ov_flags ? b->ov_flags : (int32_t *)b->field[JM_F_CON_FLAGS];
-            C.data = b->ov_data ? (T *)b->ov_data : (T *)b->field[JM_F_CON_DATA];
-            C.ws = b->ov_ws ? (T *)b->ov_ws : (T *)b->field[JM_F_WORKSPACE];
-            // per-lane friction: bound field (compact batches of the adaptive stepper read it through BatchArgs::lane_map)
-            C.friction = (const T *)b->field[JM_F_FRICTION];
-            const double omega = 2.0 * 3.14159265358979323846 * b->copt.stabilization_freq;  // abstract_constraint.cc:88-98
-            C.kp = (T)(omega * omega);
-            C.kd = (T)(2.0 * omega);
-            // user-registered constraints: gains of their own when the option says so (jm_constraint_options, ABI 6)
-            const double omega_u = 2.0 * 3.14159265358979323846 * b->copt.user_stabilization_freq;
-            C.kp_lock = b->copt.user_stabilization_freq < 0.0 ? C.kp : (T)(omega_u * omega_u);
-            C.kd_lock = b->copt.user_stabilization_freq < 0.0 ? C.kd : (T)(2.0 * omega_u);
-            C.torsion = (T)b->copt.torsion; C.reg = (T)b->copt.regularization;
-            C.tol_abs = (T)b->copt.tol_abs; C.tol_rel = (T)b->copt.tol_rel;
-            C.iter_max = b->copt.pgs_iter_max;
-            C.xl = nullptr; C.xstride = 0;  // set by the kernel (LDS)
-            C.yl = nullptr; C.ystride = 0; C.yrows = 0;
-            C.park = nullptr; C.park_rows = 0;
-            if (Topo::QUAD && b->variant == VARIANT_QUAD && R::NR > 0) launch_quad_con<Topo>(b, A, C, s);
-            else
-            {
-                bool done = false;
-                if constexpr (!Topo::QUAD)
-                    if (A.applied || A.model_lane || A.ground_h) { hipLaunchKernelGGL((jm::k_constrained<T, Topo, true>), dim3(grid), dim3(64), 0, s, A, C); done = true; }
-                if (!done) hipLaunchKernelGGL((jm::k_constrained<T, Topo, false>), dim3(grid), dim3(64), 0, s, A, C);
-            }
-        }
-        else return fail(JM_ENOTIMPL, "contacts.model = 'constraint' needs a float64 batch");
-    }
-    else if (b->variant == VARIANT_QUAD) launch_quad<T, Topo>(b, A, s);
-    else
-    {
-        bool done = false;
-        if constexpr (!Topo::QUAD && std::is_same<T, double>::value)
-            if (A.applied || A.model_lane || A.ground_h) { hipLaunchKernelGGL((jm::k_batch<T, Topo, true>), dim3(grid), dim3(64), 0, s, A); done = true; }
-        if (!done) hipLaunchKernelGGL((jm::k_batch<T, Topo, false>), dim3(grid), dim3(64), 0, s, A);
-    }
+    if (!launch_form<T, Topo>(b, A, sel, s)) return fail(JM_ERUNTIME, "this library has no kernel for the selected form");
     HIP_TRY(hipGetLastError());
     if (timed)
     {
@@ -538,6 +413,14 @@ template<class T> int32_t launch(jm_batch * b, jm::BatchArgs<T> & A, void * stre
         ++b->n_timed;
     }
     return JM_OK;
+}
+
+// the float64 / float32 switch of the entry points: `f` gets a zero of the batch's scalar type ...
+template<class F> int32_t with_dtype(const jm_batch * b, F && f) { return b->dtype == JM_F64 ? f(double()) : f(float()); }
+// ... and the launches among them: the batch's arguments, `set` the mode and what goes with it, launch
+template<class F> int32_t launch_as(jm_batch * b, void * stream, F && set)
+{
+    return with_dtype(b, [&](auto z) { auto A = make_args<decltype(z)>(b); set(A); return launch(b, A, stream); });
 }
 
 int32_t check_bound(const jm_batch * b, bool need_command)
@@ -548,10 +431,7 @@ int32_t check_bound(const jm_batch * b, bool need_command)
         return fail(JM_ECONTROLFLOW, "the command field must be bound before this call");
     return JM_OK;
 }
-}  // namespace
 
-namespace
-{
 template<class T> int32_t step_adaptive(jm_batch * b, double t_next, const jm_adaptive_options * o, int32_t new_step,
                                                int32_t command_changed, int32_t update_sensors, int32_t max_attempts,
                                                int32_t * attempts_out, void * stream)
@@ -585,18 +465,17 @@ template<class T> int32_t step_adaptive(jm_batch * b, double t_next, const jm_ad
     D.con_flags_c = b->ad_flags;
     if (constrained && (!D.con_flags || !D.con_data || !b->ad_flags))
         return fail(JM_ECONTROLFLOW, "contacts.model = 'constraint': bind con_flags / con_data, then jm_batch_bind_adaptive");
-    // branch-parallel topologies, spring-damper contacts, float64: ONE persistent launch per interval, every quad
-    // runs its robot's whole adaptive loop on the chip (jm_qdopri.h); the host only learns whether a robot ran
-    // into the attempt bound of a launch (then it launches again) and the largest attempt count
+    // the persistent form (jm_dispatch.h, select_adaptive_form): every quad runs its robot's whole adaptive loop on the chip; the
+    // host only learns whether a robot ran into the attempt bound of a launch (then it launches again) and the largest attempt count
+    auto A0 = make_args<T>(b);
+    A0.mode = jm::MODE_DYNAMICS;
+    jd::Facts facts = facts_of<T>(b, A0);
+    facts.friction = b->field[JM_F_FRICTION];   // (alone it also needs the variation kernel: only its contact law reads the field)
+    const jd::Form form = jd::select_adaptive_form(traits_of<T, Topo>(), facts, o->form == 1);
     if constexpr (Topo::QUAD && std::is_same<T, double>::value)
     {
-        if (b->variant == VARIANT_QUAD && !constrained && o->form != 1)
+        if (form != jd::DOPRI_STAGES)
         {
-            // (per-lane friction alone also needs the variation kernel: only its contact law reads A.friction)
-            const bool gen = b->field[JM_F_MODEL_LANE] || b->ground_h || (b->applied_k > 0 && b->field[JM_F_APPLIED]) ||
-                             b->field[JM_F_FRICTION];
-            auto A = make_args<T>(b);
-            A.mode = jm::MODE_DYNAMICS;
             constexpr int nth = 64 * jm::qdopri_block_waves<T, Topo>();
             const unsigned grid = (unsigned)((B + nth / 4 - 1) / (nth / 4));
             const int per_launch = 4096;
@@ -604,8 +483,8 @@ template<class T> int32_t step_adaptive(jm_batch * b, double t_next, const jm_ad
             for (;;)
             {
                 HIP_TRY(hipMemsetAsync(b->ad_count, 0, 2 * sizeof(int32_t), s));
-                if (gen) hipLaunchKernelGGL((jm::k_quad_dopri_gen<T, Topo>), dim3(grid), dim3(nth), 0, s, A, D, per_launch);
-                else hipLaunchKernelGGL((jm::k_quad_dopri<T, Topo>), dim3(grid), dim3(nth), 0, s, A, D, per_launch);
+                if (form == jd::DOPRI_GEN) hipLaunchKernelGGL((jm::k_quad_dopri_gen<T, Topo>), dim3(grid), dim3(nth), 0, s, A0, D, per_launch);
+                else hipLaunchKernelGGL((jm::k_quad_dopri<T, Topo>), dim3(grid), dim3(nth), 0, s, A0, D, per_launch);
                 HIP_TRY(hipGetLastError());
                 D.new_step = 0;
                 HIP_TRY(hipMemcpyAsync(b->ad_count_host, b->ad_count, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -735,27 +614,30 @@ int32_t jm_batch_create(const jm_model * model, int64_t batch_size, int32_t dtyp
     b->params = model->params;
     // kernel variant: limb-parallel when the topology allows it; JM_KERNEL_VARIANT=lane forces the
     // generic one-robot-per-lane kernel (A/B measurements)
-    b->variant = (Topo::QUAD && model->root_at_origin) ? VARIANT_QUAD : VARIANT_LANE;
+    b->variant = (Topo::QUAD && model->root_at_origin) ? jd::FAMILY_QUAD : jd::FAMILY_LANE;
     // (`start` / `reset` of robots with small solves: the single kernel -- its passes run on chip; jm_qcon.h, k_quad_con<1>)
     if constexpr (Topo::QUAD) b->qcon_split_start = jm::qcon_split_large<Topo>();
     if (const char * e = std::getenv("JIMINY_AMD_QCON_SPLIT")) b->qcon_split = e[0] != '0';
     if (const char * e = std::getenv("JIMINY_AMD_QCON_SPLIT_START")) b->qcon_split_start = e[0] != '0';
-    if (const char * e = std::getenv("JIMINY_AMD_QCON_SPLIT_CHUNKS"))
-    {
-        const int n = std::atoi(e);
-        b->split_chunks = n < 1 ? 1 : (n > 8 ? 8 : n);
-    }
+    b->debug_split = std::getenv("JM_DEBUG_SPLIT") != nullptr; b->split_capture = std::getenv("JIMINY_AMD_QCON_SPLIT_CAPTURE") != nullptr;
     if (const char * v = std::getenv("JM_KERNEL_VARIANT"))
-        if (std::string(v) == "lane") b->variant = VARIANT_LANE;
+        if (std::string(v) == "lane") b->variant = jd::FAMILY_LANE;
     hipError_t e = hipSetDevice(device);
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) b->n_cus = cus;
     }
     if (e == hipSuccess) e = hipMalloc(&b->d_params, b->params.size() * sizeof(double));
+    // counters of the one-lane-per-robot solve, their pinned mirror and events (a failure frees them with the batch)
+    constexpr size_t stat_bytes = 4 * jd::SplitHistory::SLOTS * sizeof(int32_t);
+    const bool counters = traits_of<double, Topo>().lane_history();
+    if (e == hipSuccess && counters) e = hipMalloc((void **)&b->lane_stat, stat_bytes);
+    if (e == hipSuccess && counters) e = hipHostMalloc((void **)&b->lane_stat_host, stat_bytes, hipHostMallocDefault);
+    for (hipEvent_t & ev : b->lane_ev) if (e == hipSuccess && counters) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess && counters) std::memset(b->lane_stat_host, 0, stat_bytes);
     if (e != hipSuccess)
     {
-        delete b;
+        jm_batch_destroy(b);
         return fail(JM_ERUNTIME, std::string("jm_batch_create: ") + hipGetErrorString(e));
     }
     const int32_t rc = upload_params(b);
@@ -775,13 +657,10 @@ int32_t jm_batch_destroy(jm_batch * b)
     if (b->ad_count) (void)hipFree(b->ad_count);
     if (b->lane_stat) (void)hipFree(b->lane_stat);
     if (b->lane_stat_host) (void)hipHostFree(b->lane_stat_host);
-    for (int i = 0; i < jm_batch::LANE_SLOTS; ++i) if (b->lane_ev[i]) (void)hipEventDestroy(b->lane_ev[i]);
+    for (hipEvent_t e : b->lane_ev) if (e) (void)hipEventDestroy(e);
     if (b->ad_flags) (void)hipFree(b->ad_flags);
     if (b->ad_count_host) (void)hipHostFree(b->ad_count_host);
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
-    if (b->split_fork) (void)hipEventDestroy(b->split_fork);
-    for (hipEvent_t e : b->split_join) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : b->split_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     delete b;
     return JM_OK;
 }
@@ -866,18 +745,7 @@ int32_t jm_batch_start(jm_batch * b, void * stream)
     if (!b) return fail(JM_EINVAL, "jm_batch_start: null batch");
     int32_t rc = check_bound(b, true);
     if (rc != JM_OK) return rc;
-    if (b->dtype == JM_F64)
-    {
-        auto A = make_args<double>(b);
-        A.mode = jm::MODE_START;
-        rc = launch<double>(b, A, stream);
-    }
-    else
-    {
-        auto A = make_args<float>(b);
-        A.mode = jm::MODE_START;
-        rc = launch<float>(b, A, stream);
-    }
+    rc = launch_as(b, stream, [](auto & A) { A.mode = jm::MODE_START; });
     if (rc == JM_OK) b->started = true;
     return rc;
 }
@@ -905,17 +773,10 @@ int32_t jm_batch_step(jm_batch * b, int32_t solver, double dt, int32_t n_substep
     if (n_substeps < 1) return fail(JM_EINVAL, "n_substeps must be >= 1");
     int32_t rc = check_bound(b, true);
     if (rc != JM_OK) return rc;
-    if (b->dtype == JM_F64)
-    {
-        auto A = make_args<double>(b);
-        A.mode = jm::MODE_STEP; A.solver = solver; A.dt = dt; A.n_sub = n_substeps;
+    return launch_as(b, stream, [&](auto & A) {
+        A.mode = jm::MODE_STEP; A.solver = solver; A.dt = (decltype(A.dt))dt; A.n_sub = n_substeps;
         A.command_changed = command_changed; A.update_sensors = update_sensors;
-        return launch<double>(b, A, stream);
-    }
-    auto A = make_args<float>(b);
-    A.mode = jm::MODE_STEP; A.solver = solver; A.dt = (float)dt; A.n_sub = n_substeps;
-    A.command_changed = command_changed; A.update_sensors = update_sensors;
-    return launch<float>(b, A, stream);
+    });
 }
 
 // ---- adaptive Dormand-Prince stepping (jm_adaptive.h)
@@ -954,9 +815,9 @@ int32_t jm_batch_step_adaptive(jm_batch * b, double t_next, const jm_adaptive_op
     int32_t rc = check_bound(b, true);
     if (rc != JM_OK) return rc;
     HIP_TRY(hipSetDevice(b->device));
-    if (b->dtype == JM_F64)
-        return step_adaptive<double>(b, t_next, options, new_step, command_changed, update_sensors, max_attempts, attempts_out, stream);
-    return step_adaptive<float>(b, t_next, options, new_step, command_changed, update_sensors, max_attempts, attempts_out, stream);
+    return with_dtype(b, [&](auto z) {
+        return step_adaptive<decltype(z)>(b, t_next, options, new_step, command_changed, update_sensors, max_attempts, attempts_out, stream);
+    });
 }
 
 int32_t jm_batch_dynamics(jm_batch * b, const void * q_in, const void * v_in, void * a_out, void * stream)
@@ -965,15 +826,9 @@ int32_t jm_batch_dynamics(jm_batch * b, const void * q_in, const void * v_in, vo
     if (!b->started)
         return fail(JM_ECONTROLFLOW, "No simulation running. Please start one before calling this method.");  // engine.cc:3594-3599
     if (Topo::NM > 0 && !b->field[JM_F_COMMAND]) return fail(JM_ECONTROLFLOW, "the command field must be bound");
-    if (b->dtype == JM_F64)
-    {
-        auto A = make_args<double>(b);
-        A.mode = jm::MODE_DYNAMICS; A.q_in = (const double *)q_in; A.v_in = (const double *)v_in; A.a_out = (double *)a_out;
-        return launch<double>(b, A, stream);
-    }
-    auto A = make_args<float>(b);
-    A.mode = jm::MODE_DYNAMICS; A.q_in = (const float *)q_in; A.v_in = (const float *)v_in; A.a_out = (float *)a_out;
-    return launch<float>(b, A, stream);
+    return launch_as(b, stream, [&](auto & A) {
+        A.mode = jm::MODE_DYNAMICS; A.q_in = (decltype(A.q_in))q_in; A.v_in = (decltype(A.v_in))v_in; A.a_out = (decltype(A.a_out))a_out;
+    });
 }
 
 int32_t jm_batch_reset_lanes(jm_batch * b, const uint8_t * lane_mask, const void * q_init, const void * v_init, void * stream)
@@ -982,15 +837,9 @@ int32_t jm_batch_reset_lanes(jm_batch * b, const uint8_t * lane_mask, const void
     if (!b->started) return fail(JM_ECONTROLFLOW, "No simulation running. Please start one before resetting lanes.");
     int32_t rc = check_bound(b, true);
     if (rc != JM_OK) return rc;
-    if (b->dtype == JM_F64)
-    {
-        auto A = make_args<double>(b);
-        A.mode = jm::MODE_RESET; A.mask = lane_mask; A.q_init = (const double *)q_init; A.v_init = (const double *)v_init;
-        return launch<double>(b, A, stream);
-    }
-    auto A = make_args<float>(b);
-    A.mode = jm::MODE_RESET; A.mask = lane_mask; A.q_init = (const float *)q_init; A.v_init = (const float *)v_init;
-    return launch<float>(b, A, stream);
+    return launch_as(b, stream, [&](auto & A) {
+        A.mode = jm::MODE_RESET; A.mask = lane_mask; A.q_init = (decltype(A.q_init))q_init; A.v_init = (decltype(A.v_init))v_init;
+    });
 }
 
 int32_t jm_batch_enable_timing(jm_batch * b, int32_t enable)

@@ -383,7 +383,7 @@ def _library_self_test_detail(model: CompiledModel, variant: int, dtype: torch.d
     n0, dt = 64, 1e-4
     probe_state = _probe_state(model, n0)
     # the branch-parallel step kernel has a one-wave-per-block instantiation for small batches and a
-    # several-waves-per-block one for large batches (jm_lib.cpp `launch_quad`): both are probed, and must
+    # several-waves-per-block one for large batches (jm_dispatch.h `select_form`): both are probed, and must
     # agree with each other lane for lane
     sizes = [n0]
     if codegen.quad_structure(model) is not None:
@@ -988,6 +988,21 @@ class BatchedEngine:
                 "another variant (JIMINY_AMD_BUILD_VARIANT).")
         _CON_VERIFIED[key] = err
 
+    @property
+    def _quad_family(self) -> bool:
+        """The batch runs on the branch-parallel kernel family (README.md, "What runs where")."""
+        return codegen.quad_structure(self.model) is not None and os.environ.get("JM_KERNEL_VARIANT") != "lane"
+
+    @property
+    def _quad_forced_to_lane(self) -> bool:
+        """A branch-parallel topology forced to the one-robot-per-lane kernels (JM_KERNEL_VARIANT=lane)."""
+        return codegen.quad_structure(self.model) is not None and not self._quad_family
+
+    def _variation_kernels_in_use(self, friction: bool, locks: bool = False) -> bool:
+        """The launches of this batch go to the variation kernels of its family: per-lane body parameters, applied forces or
+        a height map -- and, where the caller's family moves to them for it, per-lane `friction` or user constraints."""
+        return bool("model_lane" in self._fields or "applied" in self._fields or self._ground is not None or friction or locks)
+
     def _check_variation_kernels(self) -> None:
         """First use of per-lane body parameters / a height map / applied forces for this topology and contact
         model in the process: run `_variation_self_test` and refuse to run a library that fails it."""
@@ -995,13 +1010,11 @@ class BatchedEngine:
                 os.environ.get("JIMINY_AMD_SELF_TEST", "1") == "0":
             return
         # (the one-robot-per-lane kernels read the lane's friction in their only contact law: no variation form to check)
-        lane_mu = "friction" in self._fields and self._options["contacts"]["model"] != "constraint" and \
-            codegen.quad_structure(self.model) is not None and os.environ.get("JM_KERNEL_VARIANT") != "lane"
+        lane_mu = "friction" in self._fields and self._options["contacts"]["model"] != "constraint" and self._quad_family
         # (user constraints: only the branch-parallel family moves to its variation kernels for them; the lane kernel has none)
-        locks = bool(self._user_constraints) and codegen.quad_structure(self.model) is not None and \
-            os.environ.get("JM_KERNEL_VARIANT") != "lane"
+        locks = bool(self._user_constraints) and self._quad_family
         # (either family: the variation kernels -- `k_quad_gen` ..., or the variation instantiations of the one-robot-per-lane kernels)
-        if not ("model_lane" in self._fields or "applied" in self._fields or self._ground is not None or lane_mu or locks):
+        if not self._variation_kernels_in_use(lane_mu, locks):
             return
         self._gen_checked = True
         variant = self._lib_variant_index
@@ -1220,8 +1233,7 @@ class BatchedEngine:
             self._fields.pop("friction", None)
             self._lib.check(self._L.jm_batch_bind(self._batch_h, _abi.FIELD_NAMES["friction"], None))
             return
-        quad = codegen.quad_structure(self.model) is not None and os.environ.get("JM_KERNEL_VARIANT") != "lane"
-        if self._options["contacts"]["model"] != "constraint" and quad and self.dtype != torch.float64:
+        if self._options["contacts"]["model"] != "constraint" and self._quad_family and self.dtype != torch.float64:
             raise NotImplementedError("per-lane friction with the spring-damper model on a branch-parallel topology (floating base "
                                       "with limb chains) needs a float64 batch")
         f = torch.as_tensor(friction, dtype=self.dtype, device=self.device).reshape(1, -1)
@@ -1468,7 +1480,7 @@ class BatchedEngine:
             return 0
         # (the variation form of the kernel -- per-lane body parameters / friction, height map, applied forces: jm_lib.cpp
         # `step_adaptive` -- is a compilation of its own and is checked on its own)
-        gen = bool("model_lane" in self._fields or self._ground is not None or "applied" in self._fields or "friction" in self._fields)
+        gen = self._variation_kernels_in_use("friction" in self._fields)
         key = (self.model.topology_hash(), self._lib_variant_index, gen)
         if key not in _DOPRI_FORM:
             _DOPRI_FORM[key] = 0       # (the probes below are engines of the same topology)
@@ -1759,8 +1771,7 @@ class BatchedEngine:
         """Slot of the frame among the (at most four) frames that carry applied wrenches.  Any frame of the model: the
         wrench goes to the frame's parent joint, like `Engine::computeExternalForces` (engine.cc:3481-3560)."""
         fr = self.model.frame(frame_name)
-        if self.dtype != torch.float64 or (codegen.quad_structure(self.model) is not None and
-                                           os.environ.get("JM_KERNEL_VARIANT") == "lane"):
+        if self.dtype != torch.float64 or self._quad_forced_to_lane:
             raise NotImplementedError("external forces need a float64 batch (the kernels that read them are float64 "
                                       "instantiations of their own in either kernel family)")
         if frame_name not in self._force_frames:

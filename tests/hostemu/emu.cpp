@@ -250,7 +250,7 @@ template<class T, class Tp> static void run_quad_con_split(const jm::BatchArgs<T
                     };
                     if (A.mode == jm::MODE_START || A.mode == jm::MODE_RESET)
                     {
-                        // Engine::start / reset in the split form (jm_lib.cpp launch_quad_con): first pass | exact solve |
+                        // Engine::start / reset in the split form (jm_lib.cpp launch_split_start): first pass | exact solve |
                         // 3 x (pass | Gauss-Seidel) | closing evaluation
                         if (A.mode == jm::MODE_RESET && !A.mask[r]) continue;
                         C.split_e = 0;

@@ -641,9 +641,7 @@ def test_gpu_split_stepping_with_the_one_lane_per_robot_solve(gpu_device, monkey
 def test_gpu_split_stepping_of_large_solves(gpu_device, monkeypatch, solver, n_sub, B):
     """Atlas-sized solves step through three launches per evaluation (k_quad_con_split<1> | k_qcon_pgs |
     k_quad_con_split<2>, jm_qcon.h) when the batch is a multiple of 16: same states, multipliers, flags and outputs
-    as the single kernel (JIMINY_AMD_QCON_SPLIT=0) and as the oracle.  The large batch steps as four chunks on streams of
-    their own (the JIMINY_AMD_QCON_SPLIT_CHUNKS option of jm_lib.cpp, launch_quad_con; last chunk ragged): compared with the
-    single kernel."""
+    as the single kernel (JIMINY_AMD_QCON_SPLIT=0) and as the oracle.  The large batch: compared with the single kernel."""
     import torch
 
     from jiminy_amd.engine import BatchedEngine
@@ -654,7 +652,6 @@ def test_gpu_split_stepping_of_large_solves(gpu_device, monkeypatch, solver, n_s
     engines = []
     for split in ("1", "0"):
         monkeypatch.setenv("JIMINY_AMD_QCON_SPLIT", split)
-        monkeypatch.setenv("JIMINY_AMD_QCON_SPLIT_CHUNKS", "4" if B > 64 else "1")
         eng = BatchedEngine(model, B, dtype=torch.float64, device=gpu_device,
                             extra_outputs=("contact_forces", "f_external", "joint_forces", "energy", "centroidal"))
         eng.set_options({"stepper": {"odeSolver": solver, "dtMax": dt, "controllerUpdatePeriod": n_sub * dt,
