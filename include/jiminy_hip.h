@@ -482,6 +482,58 @@ int32_t jm_block_sensor_delay(int32_t dtype, int64_t batch_size, int32_t n_senso
                               uint64_t * rng_state, const double * delay, const double * jitter,
                               int32_t interpolation_order, void * stream);
 
+/* ---- DeformationEstimator observer block (ABI 10), batched: one lane = one environment.
+ * jm_block_deformation_estimator ≙ `DeformationEstimator.refresh_observation`
+ *   (python/gym_jiminy/common/gym_jiminy/common/blocks/deformation_estimator.py:831-863): from the encoders and the IMU
+ *   attitude estimates (`imu_quat`, `[4][n_imu][B]` xyzw, e.g. the state of jm_block_mahony_filter) to one deformation
+ *   quaternion per flexibility point (`out_quat`, `[4][n_flex][B]`) and, `out_rpy` not NULL, its roll-pitch-yaw angles
+ *   (`[3][n_flex][B]`, `quat_to_rpy`, utils/math.py:158-201).  Per chain of interleaved IMU / flexibility frames
+ *   `flexibility_estimator` (:139-235) = `_compute_orientation_error` (:30-76; `ignore_twist`: `compute_tilt_from_quat`
+ *   + `swing_from_vector`, utils/math.py:1045-1133, else `matrices_to_quat` :306-360 + `quat_multiply` :570-626) then
+ *   `_compute_deformation_from_deviation` (:80-134).  The rotations of the theoretical (rigid) model (:833-841) are
+ *   evaluated on the device from the description below.
+ * jm_deform_desc: the plan (host arrays, copied by jm_deform_plan_create).
+ *   Frames: frame f is the product of its segments `frame_seg_start[f] .. frame_seg_start[f + 1] - 1`; a segment is a
+ *   constant rotation `seg_rot` (row-major 3x3) followed by a joint rotation: `seg_kind` 0 none, 1 / 2 / 3 about x / y / z,
+ *   4 about the unit vector `seg_axis`, by the angle `seg_ratio * encoder[seg_enc]` (position row of that encoder in the
+ *   raw JM_F_ENCODER field `[n_enc][2][B]`; `seg_ratio` brings a motor-side encoder to the joint side).
+ *   Chains: chain c has `chain_nflex[c]` flexibility points and `chain_nflex[c] + 1 - chain_orphan[c][1]` IMUs, listed
+ *   in chain order in `chain_imu` (column of `imu_quat`) / `chain_imu_frame` (kinematic frame of that IMU) and in
+ *   `flex_frame` (kinematic parent frame of the flexibility point, :776-788) / `flex_flipped` (:132-134); output column
+ *   k is the k-th flexibility point of that concatenated order.  `chain_orphan[c]` ≙ `is_chain_orphan` (:641-647): [1] the
+ *   last flexibility point of the chain has no IMU behind it; [0] (the FIRST IMU is missing) must be 0: the reference's
+ *   block cannot be built for such a chain either (:297-307, :606-611).
+ * jm_deform_plan_create validates the description (JM_EINVAL + jm_last_error, before any device call) and uploads it;
+ * jm_block_deformation_estimator then allocates, copies and synchronises nothing: it can be captured into a HIP graph. */
+typedef struct jm_deform_desc
+{
+    int32_t n_imu;          /* columns of imu_quat */
+    int32_t n_enc;          /* sensors of the encoder field */
+    int32_t n_flex;         /* columns of the outputs = sum of chain_nflex */
+    int32_t ignore_twist;
+    int32_t n_chain;
+    const int32_t * chain_nflex;        /* [n_chain] */
+    const int32_t * chain_orphan;       /* [n_chain][2] */
+    const int32_t * chain_imu;          /* [sum of IMUs per chain] */
+    const int32_t * chain_imu_frame;    /* same */
+    const int32_t * flex_frame;         /* [n_flex] */
+    const int32_t * flex_flipped;       /* [n_flex] */
+    int32_t n_frame;
+    const int32_t * frame_seg_start;    /* [n_frame + 1], ascending, last = n_seg */
+    int32_t n_seg;
+    const int32_t * seg_kind;           /* [n_seg] */
+    const int32_t * seg_enc;            /* [n_seg], -1 where seg_kind is 0 */
+    const double * seg_rot;             /* [n_seg][9] */
+    const double * seg_axis;            /* [n_seg][3] */
+    const double * seg_ratio;           /* [n_seg] */
+} jm_deform_desc;
+typedef struct jm_deform_plan jm_deform_plan;
+int32_t jm_deform_plan_create(const jm_deform_desc * desc, jm_deform_plan ** out);
+int32_t jm_deform_plan_destroy(jm_deform_plan * plan);
+int32_t jm_block_deformation_estimator(const jm_deform_plan * plan, int32_t dtype, int64_t batch_size,
+                                       const void * encoder, const void * imu_quat, void * out_quat, void * out_rpy,
+                                       void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

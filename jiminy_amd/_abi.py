@@ -8,7 +8,7 @@ import numpy as np
 
 from .model import CompiledModel
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # error codes
 JM_OK, JM_EINVAL, JM_ERUNTIME, JM_ECONTROLFLOW = 0, -1, -2, -3
@@ -66,6 +66,19 @@ class ModelDesc(C.Structure):
         ("cframe_kind", _pi), ("cframe_joint2", _pi), ("cframe_params", _pd),
         ("n_constraint_joints", C.c_int32), ("cjoint_joint", _pi),
         ("flex_stiffness", _pd), ("flex_damping", _pd),
+    ]
+
+
+class DeformDesc(C.Structure):
+    """jm_deform_desc: the plan of the DeformationEstimator block (jiminy_amd.deformation builds it)."""
+    _fields_ = [
+        ("n_imu", C.c_int32), ("n_enc", C.c_int32), ("n_flex", C.c_int32), ("ignore_twist", C.c_int32),
+        ("n_chain", C.c_int32),
+        ("chain_nflex", _pi), ("chain_orphan", _pi), ("chain_imu", _pi), ("chain_imu_frame", _pi),
+        ("flex_frame", _pi), ("flex_flipped", _pi),
+        ("n_frame", C.c_int32), ("frame_seg_start", _pi),
+        ("n_seg", C.c_int32), ("seg_kind", _pi), ("seg_enc", _pi),
+        ("seg_rot", _pd), ("seg_axis", _pd), ("seg_ratio", _pd),
     ]
 
 

@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     "jm_batch_set_constraint_options", "jm_batch_constraint_rows", "jm_block_sensor_delay",
     "jm_batch_set_ground", "jm_batch_set_applied_frames", "jm_batch_set_joint_locks", "jm_block_pd_adapter", "jm_block_motor_safety_limit",
     "jm_block_model_bias", "jm_engine_rng_seed",
+    "jm_deform_plan_create", "jm_deform_plan_destroy", "jm_block_deformation_estimator",
 )
 
 
@@ -100,6 +101,9 @@ class HipLibrary:
         L.jm_batch_set_ground.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]
         L.jm_batch_set_applied_frames.argtypes = [vp, C.c_int32, dp, ip]
         L.jm_batch_set_joint_locks.argtypes = [vp, C.c_int32]
+        L.jm_deform_plan_create.argtypes = [C.POINTER(_abi.DeformDesc), C.POINTER(vp)]
+        L.jm_deform_plan_destroy.argtypes = [vp]
+        L.jm_block_deformation_estimator.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

@@ -14,6 +14,10 @@ Two forms of the per-controller-tick blocks:
   tensors live and serve as the readable specification the kernels are tested against.
 `HipBlocks.pd_adapter` / `HipBlocks.motor_safety_limit` are the `PDAdapter` / `MotorSafetyLimit` blocks as single
 launches; `pd_adapter` below is the tensor-program form.
+
+`DeformationEstimator` is the observer block of that name (blocks/deformation_estimator.py): one HIP launch
+(csrc/jm_deform.h behind `jm_block_deformation_estimator`) driven by a plan that jiminy_amd/deformation.py builds on the host.
+It has no tensor-program form: its specification is the reference's own output (tests/golden/ref_deformation.npz).
 """
 from __future__ import annotations
 
@@ -107,6 +111,83 @@ class HipBlocks:
             self._dtype, self._eng.batch_size, self._M, self._ptr(self._eng.field("encoder")), self._enc.ctypes.data_as(ip),
             self._ptr(command), *[x.ctypes.data_as(dp) for x in a], self._lim.ctypes.data_as(dp), self._ptr(out),
             self._eng._stream()))
+
+
+class DeformationEstimator:
+    """≙ `gym_jiminy.common.blocks.DeformationEstimator` (blocks/deformation_estimator.py:416-863), batched: from the
+    encoders of the engine and IMU attitude estimates (`[4][n_imu][B]` xyzw in the order of the model's IMU sensors, e.g.
+    the state of the Mahony filter) to one deformation quaternion per flexibility point.
+
+    `quat` `[4][n_flex][B]` (the identity until the first `refresh`, :767) and `rpy` `[3][n_flex][B]` (`compute_rpy`) are
+    the observation; their columns follow `flexibility_frame_names`, which is NOT the order of `flex_frame_names` but the
+    order of the kinematic chains (:613-616).  Deviation from the reference: the compiled model must have a flexibility
+    joint at every frame of `flex_frame_names` (`NotImplementedError` otherwise; see jiminy_amd/deformation.py)."""
+
+    def __init__(self, engine, imu_frame_names, flex_frame_names, ignore_twist: bool = True, compute_rpy: bool = True) -> None:
+        import ctypes as C
+
+        from . import _abi, deformation
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.plan = deformation.build_plan(engine.model, imu_frame_names, flex_frame_names, ignore_twist, compute_rpy)
+        self.ignore_twist, self.compute_rpy = bool(ignore_twist), bool(compute_rpy)
+        self.flexibility_frame_names = list(self.plan.flexibility_frame_names)
+        self._n_imu = len(engine.model.sensors["ImuSensor"])
+        n_flex, B = self.plan.n_flex, engine.batch_size
+        self.quat = torch.zeros((4, n_flex, B), dtype=engine.dtype, device=engine.device)
+        self.quat[3] = 1.0
+        self.rpy = torch.zeros((3, n_flex, B), dtype=engine.dtype, device=engine.device) if compute_rpy else None
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_deform_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        """≙ `DeformationEstimator.fieldnames` (:819-829)."""
+        names = {"quat": [[f"{name}.Quat{e}" for name in self.flexibility_frame_names] for e in ("x", "y", "z", "w")]}
+        if self.compute_rpy:
+            names["rpy"] = [[".".join((name, e)) for name in self.flexibility_frame_names] for e in ("Roll", "Pitch", "Yaw")]
+        return names
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The identity (and zero angles) on the masked lanes, by selection; on every lane without a mask."""
+        unit = torch.zeros_like(self.quat)
+        unit[3] = 1.0
+        if lane_mask is None:
+            self.quat.copy_(unit)
+            if self.rpy is not None:
+                self.rpy.zero_()
+        else:
+            m = lane_mask[None, None, :]
+            self.quat.copy_(torch.where(m, unit, self.quat))
+            if self.rpy is not None:
+                self.rpy.copy_(torch.where(m, torch.zeros_like(self.rpy), self.rpy))
+
+    def refresh(self, imu_quat: torch.Tensor) -> None:
+        """≙ `refresh_observation` (:831-863): one launch on the engine's stream; no allocation, copy or synchronisation."""
+        eng = self._eng
+        if tuple(imu_quat.shape) != (4, self._n_imu, eng.batch_size):
+            raise ValueError(f"imu_quat must have shape (4, {self._n_imu}, {eng.batch_size})")
+        for t in (imu_quat, self.quat):
+            if not t.is_contiguous() or t.device != eng.device or t.dtype != eng.dtype:
+                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+        vp = self._C.c_void_p
+        self._check(self._L.jm_block_deformation_estimator(
+            self._plan, self._dtype, eng.batch_size, vp(eng.field("encoder").data_ptr()), vp(imu_quat.data_ptr()),
+            vp(self.quat.data_ptr()), None if self.rpy is None else vp(self.rpy.data_ptr()), eng._stream()))
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_deform_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
 
 
 def integrate_zoh(state: torch.Tensor, state_min: torch.Tensor, state_max: torch.Tensor,

@@ -27,12 +27,13 @@
 #include "jm_qcon.h"
 #include "jm_pack.h"
 #include "jm_blocks.h"
+#include "jm_deform.h"
 #include "jm_adaptive.h"
 #include "jm_qdopri.h"
 #include "jm_random.h"
 #include "jm_dispatch.h"
 
-#define JM_ABI_VERSION 9
+#define JM_ABI_VERSION 10
 
 #ifdef JM_SPLIT_CONSTRAINT
 // the constraint-model kernel is instantiated by jm_lib_constraint.cpp (compiled in parallel)
@@ -975,6 +976,66 @@ int32_t jm_block_motor_safety_limit(int32_t dtype, int64_t B, int32_t M, const v
     else
         hipLaunchKernelGGL((jm::k_motor_safety_limit<float>), dim3(grid), dim3(256), 0, s, p, (const float *)encoder,
                            (const float *)command, (float *)out, (long long)B);
+    HIP_TRY(hipGetLastError());
+    return JM_OK;
+}
+
+// ---- DeformationEstimator: the plan is validated, packed and uploaded once; the call is one launch
+struct jm_deform_plan
+{
+    int32_t * d_it = nullptr;
+    double * d_dt = nullptr;
+    int n_imu = 0, n_flex = 0, ignore_twist = 0;
+};
+
+int32_t jm_deform_plan_create(const jm_deform_desc * desc, jm_deform_plan ** out)
+{
+    if (!out) return fail(JM_EINVAL, "jm_deform_plan_create: null argument");
+    *out = nullptr;
+    std::vector<int32_t> it;
+    std::vector<double> dt;
+    std::string why;
+    if (!jm::deform_pack(desc, it, dt, why)) return fail(JM_EINVAL, why);
+    jm_deform_plan * p = new (std::nothrow) jm_deform_plan;
+    if (!p) return fail(JM_ERUNTIME, "out of host memory");
+    p->n_imu = desc->n_imu; p->n_flex = desc->n_flex; p->ignore_twist = desc->ignore_twist != 0;
+    hipError_t e = hipMalloc((void **)&p->d_it, it.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_dt, dt.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(p->d_it, it.data(), it.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_dt, dt.data(), dt.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)jm_deform_plan_destroy(p);
+        return fail(JM_ERUNTIME, std::string("jm_deform_plan_create: ") + hipGetErrorString(e));
+    }
+    *out = p;
+    return JM_OK;
+}
+
+int32_t jm_deform_plan_destroy(jm_deform_plan * p)
+{
+    if (!p) return JM_OK;
+    if (p->d_it) (void)hipFree(p->d_it);
+    if (p->d_dt) (void)hipFree(p->d_dt);
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_deformation_estimator(const jm_deform_plan * p, int32_t dtype, int64_t B, const void * encoder,
+                                       const void * imu_quat, void * out_quat, void * out_rpy, void * stream)
+{
+    if (!p || !encoder || !imu_quat || !out_quat) return fail(JM_EINVAL, "jm_block_deformation_estimator: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad dtype");
+    const jm::DeformArgs a{p->d_it, p->d_dt, p->n_imu, p->n_flex, p->ignore_twist};
+    const unsigned grid = (unsigned)((B + 255) / 256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (dtype == JM_F64)
+        hipLaunchKernelGGL((jm::k_deformation_estimator<double>), dim3(grid), dim3(256), 0, s, a, (const double *)encoder,
+                           (const double *)imu_quat, (double *)out_quat, (double *)out_rpy, (long long)B);
+    else
+        hipLaunchKernelGGL((jm::k_deformation_estimator<float>), dim3(grid), dim3(256), 0, s, a, (const float *)encoder,
+                           (const float *)imu_quat, (float *)out_quat, (float *)out_rpy, (long long)B);
     HIP_TRY(hipGetLastError());
     return JM_OK;
 }

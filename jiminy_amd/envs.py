@@ -491,7 +491,8 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                  kp: Any, kd: Any, mahony_kp: float = 1.0, mahony_ki: float = 0.1,
                  joint_position_margin: float = 0.0, joint_velocity_limit: float = float("inf"),
                  joint_acceleration_limit: Optional[float] = None,
-                 safety_limit: Optional[Dict[str, float]] = None, **kw: Any) -> None:
+                 safety_limit: Optional[Dict[str, float]] = None,
+                 deformation_estimator: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
         opts = kw.pop("engine_options", None) or {}
         st = dict(opts.get("stepper", {}))
         st.setdefault("controllerUpdatePeriod", control_dt)
@@ -561,6 +562,21 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                 hi=np.array([model.position_upper[m.idx_q] * m.reduction for m in model.motors]) - red * margin,
                 vlim=np.minimum(np.array([m.velocity_limit for m in model.motors]), red * vmax))
 
+        # optional `DeformationEstimator` observer behind the Mahony filter (gym_jiminy blocks/deformation_estimator.py):
+        # `dict(imu_frame_names=..., flex_frame_names=..., ignore_twist=True, compute_rpy=True, update_ratio=1 | -1)`; it reads
+        # `imu_quat` after the filter of every controller tick (`update_ratio` 1) or once per environment step (-1)
+        self._deform = None
+        if deformation_estimator is not None:
+            if self._hip_blocks is None:
+                raise NotImplementedError("the deformation estimator runs as a HIP block")
+            cfg = dict(deformation_estimator)
+            ratio = int(cfg.pop("update_ratio", 1))
+            if ratio not in (1, -1):
+                raise NotImplementedError("deformation_estimator: update_ratio must be 1 (every controller tick) or -1 "
+                                          "(every environment step)")
+            self._deform = blocks.DeformationEstimator(self.engine, **cfg)
+            self._deform_every_tick = ratio == 1
+
     def _encoders(self) -> torch.Tensor:
         enc = self.engine.sensor_measurements["EncoderSensor"]   # (2, n_enc, B)
         return enc[:, self._enc_idx]
@@ -594,6 +610,8 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                 t.copy_(torch.where(m, torch.zeros_like(t), t))
             for t in (self._accel, self._torque):
                 t.copy_(torch.where(lane_mask[None, :], torch.zeros_like(t), t))
+        if self._deform is not None:
+            self._deform.reset(lane_mask)
 
     # ------------------------------------------------------------------ HIP-graph replay of one environment step
     def enable_graph(self, enable: bool = True, whole_step: bool = False) -> None:
@@ -729,14 +747,23 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
             if hb is not None:
                 hb.mahony_filter(self.imu_quat, self._omega, self._cf, self._bias,
                                  self.mahony_kp, self.mahony_ki, self.control_dt)
+                if self._deform is not None and self._deform_every_tick:
+                    self._deform.refresh(self.imu_quat)
             else:
                 imu = self.engine.sensor_measurements["ImuSensor"]     # (6, n_imu, B)
                 blocks.mahony_filter(self.imu_quat, self._omega, self._cf, imu[:3], imu[3:], self._bias,
                                      self.mahony_kp, self.mahony_ki, self.control_dt)
+        if self._deform is not None and not self._deform_every_tick:
+            self._deform.refresh(self.imu_quat)
 
     def observation(self) -> ObsType:
         obs = super().observation()
         obs["features"] = {"mahony_filter": self.imu_quat.permute(2, 0, 1)}
+        if self._deform is not None:
+            est = {"quat": self._deform.quat.permute(2, 0, 1)}
+            if self._deform.rpy is not None:
+                est["rpy"] = self._deform.rpy.permute(2, 0, 1)
+            obs["features"]["deformation_estimator"] = est
         obs["actions"] = {"pd_controller": self.command_state[:2].permute(2, 0, 1)}
         return obs
 
