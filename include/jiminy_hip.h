@@ -228,9 +228,11 @@ enum {
                               unbound = the model's own */
     JM_F_APPLIED = 22,     /* [6 * K] in, optional: world-aligned (force, moment) applied at K <= 4 frames of any
                               joint (jm_batch_set_applied_frames), i.e. the current value of the impulse /
-                              profile forces of core/src/engine/engine.cc:1838-2016 (the caller owns their time
-                              schedule and cuts the launches at their breakpoints); every topology (the
-                              one-robot-per-lane kernels: ABI 9) */
+                              profile forces of core/src/engine/engine.cc:1838-2016.  These are HELD values: the
+                              caller owns their time schedule and cuts the launches at their breakpoints.  Forces that
+                              are a spline of time need no schedule: jm_batch_set_process_forces (ABI 11), which the
+                              kernels evaluate inside every dynamics evaluation and add to these rows.  Every topology
+                              (the one-robot-per-lane kernels: ABI 9) */
     JM_F_GROUND_OFFSET = 23, /* [2] in, optional: (x, y) added to the world position at which every lane samples the height map
                               of jm_batch_set_ground -- every environment its own patch of one large terrain, the batched
                               form of one `world.groundProfile` per environment instance (gym_jiminy: a new random
@@ -240,7 +242,13 @@ enum {
                               WalkerJiminyEnv._setup does per episode (gym_jiminy envs/locomotion.py:288-296); read by
                               Engine::computeInternalDynamics' flexibility efforts (core/src/engine/engine.cc:3365-3391);
                               unbound = jm_model_desc::flex_stiffness / flex_damping */
-    JM_F_COUNT = 25
+    JM_F_LANE_TIME = 25,   /* [1] float64 in/out, needed with process forces (ABI 11): the time of every lane at the start of
+                              its next integrator step.  Kept by the kernels while process forces are registered:
+                              `start` sets it to 0, every integrator step of a step launch advances it by `dt` (sub-steps
+                              of one launch included), `reset_lanes` sets it to 0 for the masked lanes -- engine time for the
+                              lanes never re-initialised, episode time for the others.  Every lane stores its own value, so a
+                              captured graph carries no time argument. */
+    JM_F_COUNT = 26
 };
 
 /* ---- `contacts.model = "constraint"` (the reference's default contact model, engine.h:273) and the
@@ -316,6 +324,25 @@ int32_t jm_batch_set_joint_locks(jm_batch * batch, int32_t on);
  * Every dynamics evaluation adds the wrench to `fext[parent joint]` in the joint frame, like
  * `Engine::computeExternalForces` (engine.cc:3481-3560) through `convertForceGlobalFrameToJoint`. */
 int32_t jm_batch_set_applied_frames(jm_batch * batch, int32_t k, const double * offsets, const int32_t * joints);
+/* Process forces (ABI 11): wrench components that are a function of time, evaluated by the kernels inside EVERY dynamics
+ * evaluation at the time of that evaluation, the way Engine::computeExternalForces calls a profile force
+ * (core/src/engine/engine.cc:3482-3494) -- a(t+) refresh at t, RK4 stages at t + dt/2, t + dt/2, t + dt, the end-of-step
+ * evaluation of either solver at t + dt (abstract_runge_kutta_stepper.cc:33-73, euler_explicit_stepper.cc:5-21), `start`,
+ * `reset_lanes` and `dynamics` at the lane's current time; t = JM_F_LANE_TIME.  Component `row % 6` (force x y z, moment x y z,
+ * world aligned) of frame `row / 6` of jm_batch_set_applied_frames is its JM_F_APPLIED value (zero when that field is unbound)
+ * plus `scale * p(t)`, p the periodic cubic Hermite spline of PeriodicGaussianProcess (core/src/utilities/random.cc:322-458)
+ * through `n_knots` knots `knot_spacing` apart: `values`, `grads` = device arrays `[n_knots][B]` of float64, one realisation
+ * per lane, read at every evaluation (the caller may refill them in place between launches).  K <= 4, K = 0 disables; refused
+ * while a simulation is running, on float32 batches and by the adaptive stepper. */
+typedef struct jm_process_force {
+    int32_t row;            /* 6 * frame + component */
+    int32_t n_knots;
+    double knot_spacing;    /* period = n_knots * knot_spacing */
+    double scale;
+    const double * values;  /* [n_knots][B] */
+    const double * grads;   /* [n_knots][B] time derivatives at the knots */
+} jm_process_force;
+int32_t jm_batch_set_process_forces(jm_batch * batch, int32_t k, const jm_process_force * forces);
 /* Lend a device pointer for one field; NULL unbinds an optional output. */
 int32_t jm_batch_bind(jm_batch * batch, int32_t field, void * device_ptr);
 

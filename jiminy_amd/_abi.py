@@ -8,7 +8,7 @@ import numpy as np
 
 from .model import CompiledModel
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # error codes
 JM_OK, JM_EINVAL, JM_ERUNTIME, JM_ECONTROLFLOW = 0, -1, -2, -3
@@ -27,7 +27,7 @@ CONTACT_MODELS = {"spring_damper": JM_CONTACT_SPRING_DAMPER, "constraint": JM_CO
  JM_F_CONTACT_FORCES, JM_F_IMU, JM_F_FORCE, JM_F_CONTACT, JM_F_ENCODER, JM_F_EFFORT,
  JM_F_ENERGY, JM_F_JOINT_FORCES, JM_F_CENTROIDAL, JM_F_STATUS, JM_F_WORKSPACE,
  JM_F_CON_FLAGS, JM_F_CON_DATA, JM_F_FRICTION, JM_F_MODEL_LANE, JM_F_APPLIED, JM_F_GROUND_OFFSET, JM_F_FLEXIBILITY,
- JM_F_COUNT) = range(26)
+ JM_F_LANE_TIME, JM_F_COUNT) = range(27)
 
 FIELD_NAMES = {
     "q": JM_F_Q, "v": JM_F_V, "a": JM_F_A, "command": JM_F_COMMAND, "u_motor": JM_F_U_MOTOR,
@@ -37,11 +37,17 @@ FIELD_NAMES = {
     "centroidal": JM_F_CENTROIDAL, "status": JM_F_STATUS, "workspace": JM_F_WORKSPACE,
     "con_flags": JM_F_CON_FLAGS, "con_data": JM_F_CON_DATA, "friction": JM_F_FRICTION,
     "model_lane": JM_F_MODEL_LANE, "applied": JM_F_APPLIED, "ground_offset": JM_F_GROUND_OFFSET,
-    "flexibility": JM_F_FLEXIBILITY,
+    "flexibility": JM_F_FLEXIBILITY, "lane_time": JM_F_LANE_TIME,
 }
 
 _pi = C.POINTER(C.c_int32)
 _pd = C.POINTER(C.c_double)
+
+
+class ProcessForce(C.Structure):
+    """jm_process_force: one spline component of an applied wrench (jm_batch_set_process_forces)."""
+    _fields_ = [("row", C.c_int32), ("n_knots", C.c_int32), ("knot_spacing", C.c_double), ("scale", C.c_double),
+                ("values", C.c_void_p), ("grads", C.c_void_p)]
 
 
 class ModelDesc(C.Structure):

@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "jm_batch_set_ground", "jm_batch_set_applied_frames", "jm_batch_set_joint_locks", "jm_block_pd_adapter", "jm_block_motor_safety_limit",
     "jm_block_model_bias", "jm_engine_rng_seed",
     "jm_deform_plan_create", "jm_deform_plan_destroy", "jm_block_deformation_estimator",
+    "jm_batch_set_process_forces",
 )
 
 
@@ -101,6 +102,7 @@ class HipLibrary:
         L.jm_batch_set_ground.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]
         L.jm_batch_set_applied_frames.argtypes = [vp, C.c_int32, dp, ip]
         L.jm_batch_set_joint_locks.argtypes = [vp, C.c_int32]
+        L.jm_batch_set_process_forces.argtypes = [vp, C.c_int32, C.POINTER(_abi.ProcessForce)]
         L.jm_deform_plan_create.argtypes = [C.POINTER(_abi.DeformDesc), C.POINTER(vp)]
         L.jm_deform_plan_destroy.argtypes = [vp]
         L.jm_block_deformation_estimator.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp]

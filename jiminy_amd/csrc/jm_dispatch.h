@@ -46,6 +46,7 @@ struct Facts
     bool capturing, torsion;            // the stream is being captured into a graph; contacts.torsion >= eps (four-row contact blocks)
     bool split, split_start, split_capture;   // JIMINY_AMD_QCON_SPLIT, _SPLIT_START, _SPLIT_CAPTURE as read at creation
     bool cooling;                       // verdict of the history: this step stays with the single kernel (!SplitHistory::allowed())
+    bool process = false;               // process forces registered (jm_batch_set_process_forces): spline wrench components the kernels evaluate
 };
 
 // `counters`, SPLIT_STEP*: the solve counts into a slot of the history
@@ -56,7 +57,7 @@ struct Selection { Form form; bool counters; const char * refusal; };
 // locks: the branch-parallel constraint kernels of topologies that never step in the split form (jm::qcon_locks).
 constexpr bool needs_variation(const Traits & t, const Facts & f)
 {
-    if (f.model_lane || f.ground || f.applied) return true;
+    if (f.model_lane || f.ground || f.applied || f.process) return true;
     if (f.family != FAMILY_QUAD) return false;
     return (f.constraint && f.con_rows) ? (f.joint_locks && !t.qcon_split) : f.friction;
 }
@@ -71,6 +72,7 @@ constexpr Selection select_form(const Traits & t, const Facts & f)
     if (f.model_lane && !own) return {REFUSED, false, "per-lane body parameters need a float64 batch (and, on a branch-parallel topology, its own kernels)"};
     if (f.friction && quad && !f.f64) return {REFUSED, false, "per-lane friction on a branch-parallel topology needs a float64 batch"};
     if (f.applied && !own) return {REFUSED, false, "applied wrenches need a float64 batch (and, on a branch-parallel topology, its own kernels)"};
+    if (f.process && !own) return {REFUSED, false, "process forces need a float64 batch (and, on a branch-parallel topology, its own kernels)"};
     // constraint model, float64 only: the reference's precision; its PGS tolerances are below float32 round-off
     if (f.constraint && !f.f64) return {REFUSED, false, "contacts.model = 'constraint' needs a float64 batch"};
     const bool gen = needs_variation(t, f);
@@ -78,7 +80,7 @@ constexpr Selection select_form(const Traits & t, const Facts & f)
     if (f.constraint && quad && f.con_rows)
     {
         // split forms: plain inputs, whole waves of 16 robots, never a compact batch
-        const bool fits = t.qcon_split && f.split && !(f.model_lane || f.applied || f.ground) && (f.B & 15) == 0 && !f.compact;
+        const bool fits = t.qcon_split && f.split && !(f.model_lane || f.applied || f.process || f.ground) && (f.B & 15) == 0 && !f.compact;
         if (fits && init && f.split_start) return {SPLIT_START, false, nullptr};
         // small solves (one lane per robot): only while every solve of the batch fits that form and the solves are long (the
         // history decides); a captured step keeps one form for all its replays, the single kernel; torsion rows never fit

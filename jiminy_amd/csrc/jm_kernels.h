@@ -141,6 +141,9 @@ template<class T> struct BatchArgs
     // `[6 K][B]` at the frame offsets `applied_p` (root joint frame), K <= 4
     const T * applied;
     int applied_k;
+    // process forces (jm_batch_set_process_forces): offset of their block in the parameter block `P`, 0 = none (ProcBlock below).
+    // (An int in what was padding: the size of this struct is part of the footprint of the kernels that keep it in scratch.)
+    int proc_off = 0;
     T applied_p[12];
     int applied_joint[4];   // parent joint of every frame: the wrench goes to that joint (engine.cc:3481-3560)
     // `[1][B]` ground friction coefficient of every lane (spring-damper model; the constraint model reads its own
@@ -165,6 +168,72 @@ constexpr int LANE_STRIDE = 1;
 #else
 constexpr int LANE_STRIDE = 64;
 #endif
+// ---- process forces (jm_batch_set_process_forces, ABI 11): component `row % 6` of the wrench on applied frame `row / 6` is the
+// held `applied` value (if bound) + scale * spline(time of the dynamics evaluation), the spline a periodic cubic Hermite one
+// tabulated per lane, `[n][B]` values and time derivatives, knot spacing h (PeriodicGaussianProcess, random.cc:322-458).  The
+// profile force of the reference is a function of time called inside every dynamics evaluation (Engine::computeExternalForces,
+// engine.cc:3482-3494).  Variation instantiations only, float64.  The description sits in the parameter block at
+// P[BatchArgs::proc_off ...] (uniform: scalar loads), pointers as the bit pattern of a scalar:
+//   [0] K (1..4) | [1] lane time `[1][B]` (JM_F_LANE_TIME: the lane's time at the start of the integrator step, kept by these kernels)
+//   per component i, at [2 + 6 i]: row | n | h | scale | values | grads
+constexpr int JM_PROC_BLOCK = 2 + 6 * 4;
+template<class T> struct ProcBlock
+{
+    CPtr<T> p;
+    template<class U> static JM_DEV U * as_ptr(T x)
+    {
+        if constexpr (sizeof(T) == sizeof(U *)) return __builtin_bit_cast(U *, x);
+        else return nullptr;
+    }
+    JM_DEV int k() const { return (int)p[0]; }
+    JM_DEV T * lane_time() const { return as_ptr<T>(p[1]); }
+    JM_DEV int row(int i) const { return (int)p[2 + 6 * i]; }
+    JM_DEV int n(int i) const { return (int)p[3 + 6 * i]; }
+    JM_DEV T h(int i) const { return p[4 + 6 * i]; }
+    JM_DEV T scale(int i) const { return p[5 + 6 * i]; }
+    JM_DEV const T * values(int i) const { return as_ptr<const T>(p[6 + 6 * i]); }
+    JM_DEV const T * grads(int i) const { return as_ptr<const T>(p[7 + 6 * i]); }
+};
+template<class T> JM_DEV ProcBlock<T> proc_block(const BatchArgs<T> & A) { return {(CPtr<T>)A.P + A.proc_off}; }
+// Process force `i` at time `t`, for the lane whose column of the tables is `lane` of `stride`: the interpolation of
+// jiminy_amd/processes.py `__call__` with its order of operations, times the scale.
+template<class T> JM_DEV T process_force_value(const ProcBlock<T> & pb, int i, T t, long long stride, long long lane)
+{
+    const int n = pb.n(i);
+    const T h = pb.h(i);
+    const T period = (T)n * h;
+    T u = ::fmod(t, period);
+    if (u < T(0)) u += period;
+    const T quot = u / h;
+    const T fl = ::floor(quot);
+    const T r = quot - fl;
+    int left = (int)fl;
+    left = left < 0 ? 0 : (left > n - 1 ? n - 1 : left);
+    const int right = left + 1 == n ? 0 : left + 1;
+    const T * const y = pb.values(i) + lane;
+    const T * const g = pb.grads(i) + lane;
+    const T yl = y[(long long)left * stride], yr = y[(long long)right * stride];
+    const T gl = g[(long long)left * stride], gr = g[(long long)right * stride];
+    const T dy = yr - yl;
+    const T a = gl * h - dy;
+    const T b = -gr * h + dy;
+    return pb.scale(i) * (yl + r * ((T(1) - r) * ((T(1) - r) * a + r * b) + dy));
+}
+// the process forces that act on applied frame `frame`, added to its held wrench (F, M)
+template<class T> JM_DEV void add_process_forces(const BatchArgs<T> & A, int frame, T t, long long stride, long long lane, V3<T> & F, V3<T> & M)
+{
+    const ProcBlock<T> pb = proc_block(A);
+    const int k = pb.k();
+    for (int i = 0; i < k; ++i)
+    {
+        const int c = pb.row(i) - 6 * frame;
+        if (c < 0 || c > 5) continue;
+        const T x = process_force_value(pb, i, t, stride, lane);
+        F.x += c == 0 ? x : T(0); F.y += c == 1 ? x : T(0); F.z += c == 2 ? x : T(0);
+        M.x += c == 3 ? x : T(0); M.y += c == 4 ? x : T(0); M.z += c == 5 ? x : T(0);
+    }
+}
+
 // ---------------------------------------------------------------- per-lane working set
 template<class T, class Tp> struct Work
 {
@@ -205,7 +274,8 @@ template<class T, class Tp> struct Work
     // lose those terms at compile time (7-joint arm: 0.099 against 0.121 ms per launch with the test in the only instantiation)
     static constexpr bool APPLIED = false;
 };
-template<class T, class Tp> struct WorkA : Work<T, Tp> { static constexpr bool APPLIED = true; };
+// (`t_eval`: time of the dynamics evaluation, for the process forces)
+template<class T, class Tp> struct WorkA : Work<T, Tp> { static constexpr bool APPLIED = true; T t_eval; };
 // working set of the constraint contact model (jm_constraint.h): keeps the factorised root block
 template<class T, class Tp> struct WorkC : Work<T, Tp>
 {
@@ -213,7 +283,7 @@ template<class T, class Tp> struct WorkC : Work<T, Tp>
     T rootdinv[6];
     static constexpr bool CONSTRAINED = true;
 };
-template<class T, class Tp> struct WorkCA : WorkC<T, Tp> { static constexpr bool APPLIED = true; };
+template<class T, class Tp> struct WorkCA : WorkC<T, Tp> { static constexpr bool APPLIED = true; T t_eval; };
 // evaluation policy of lane_run: plain (spring-damper contacts) or constraint contact model
 template<class T> struct NoConArgs {};
 struct NoCon
@@ -631,19 +701,24 @@ JM_DEV void eval_kinematics(CPtr<T> P, const T * q, const T * v, const T * cmd, 
     });
     // ---- impulse / profile forces (Engine::computeExternalForces, engine.cc:3481-3560): the world-aligned wrench applied at
     // a frame goes to the frame's parent joint, in the joint frame (convertForceGlobalFrameToJoint, utilities/pinocchio.cc:794-809)
+    // (the held `applied` rows + the process forces evaluated at the time of this evaluation)
     if constexpr (W::APPLIED)
-    if (A_.applied && A_.applied_k > 0)
+    if (A_.applied_k > 0)
     {
         const BatchArgs<T> & A = A_;
         const long long st = A.lane_map ? A.B_full : A.B;
-        const T * const a0 = A.applied + lane_g();
         static_for<1, NJ>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             for (int i = 0; i < A.applied_k; ++i)
             {
                 if (A.applied_joint[i] != j) continue;
-                const T * a = a0 + (long long)(6 * i) * st;
-                const V3<T> F = {a[0], a[st], a[2 * st]}, M = {a[3 * st], a[4 * st], a[5 * st]};
+                V3<T> F = zero3<T>(), M = zero3<T>();
+                if (A.applied)
+                {
+                    const T * a = A.applied + lane_g() + (long long)(6 * i) * st;
+                    F = {a[0], a[st], a[2 * st]}; M = {a[3 * st], a[4 * st], a[5 * st]};
+                }
+                if (A.proc_off > 0) add_process_forces(A, i, w.t_eval, st, lane_g(), F, M);
                 const V3<T> p = {A.applied_p[3 * i], A.applied_p[3 * i + 1], A.applied_p[3 * i + 2]};
                 Sp<T> f;
                 f.l = tmul(w.oMi[j].R, F);
@@ -1307,6 +1382,19 @@ JM_DEV void lane_run(const BatchArgs<T> & A, long long lane, T * sb,
         static_for<0, NQ>([&](auto ic) { A.q[decltype(ic)::value * B + lane] = A.q_init[decltype(ic)::value * B + lane]; });
         static_for<0, NV>([&](auto ic) { A.v[decltype(ic)::value * B + lane] = A.v_init[decltype(ic)::value * B + lane]; });
     }
+    // process forces: `tl` = the lane's time (JM_F_LANE_TIME), 0 at `start` and for the lanes of a reset; every evaluation
+    // below reads them at its own time (w.t_eval)
+    T tl = T(0);
+    constexpr bool PROC = CON::template WorkT<T, Tp>::APPLIED;
+    if constexpr (PROC)
+    {
+        if (A.proc_off > 0)
+        {
+            if (A.mode == MODE_START || A.mode == MODE_RESET) proc_block(A).lane_time()[lane] = T(0);
+            else tl = proc_block(A).lane_time()[lane];
+        }
+        w.t_eval = tl;
+    }
     // The plain kernel runs the other modes through the loop below as ONE evaluation of the "refresh a(t+)" kind
     // (k = -1): a single copy of the evaluation and of the output pass in the kernel instead of two.
     if (CON::ON && A.mode != MODE_STEP)
@@ -1400,6 +1488,12 @@ JM_DEV void lane_run(const BatchArgs<T> & A, long long lane, T * sb,
                 else { incv[i] = aw * kv; vs[i] = v0 + aw * ka; sb[(2 * NV + i) * SBSr] = vs[i]; }
             });
             integrate_q<T, Tp>(P, q0, incv, qs);
+            // time of the evaluation (abstract_runge_kutta_stepper.cc:33-73, c = 1/2 1/2 1; euler_explicit_stepper.cc:5-21)
+            if constexpr (PROC)
+            {
+                if (k == 3) tl = tl + dt;
+                w.t_eval = (k == 3) ? tl : tl + (k == 2 ? dt : dt * T(0.5));
+            }
             if (k == 3)
             {
                 static_for<0, NQ>([&](auto ic) { A.q[decltype(ic)::value * B + lane] = qs[decltype(ic)::value]; });
@@ -1411,6 +1505,8 @@ JM_DEV void lane_run(const BatchArgs<T> & A, long long lane, T * sb,
         if (k == -1 || k == 3)
             static_for<0, NV>([&](auto ic) { adst[decltype(ic)::value * B + lane] = as[decltype(ic)::value]; });
     }
+    if constexpr (PROC)
+        if (stepping && A.proc_off > 0 && n_evals > 0) proc_block(A).lane_time()[lane] = tl;
     if constexpr (CON::ON)
     {
         // constraint model: kinematics of its own at the closing state + the forces of the multipliers the closing

@@ -33,7 +33,7 @@
 #include "jm_random.h"
 #include "jm_dispatch.h"
 
-#define JM_ABI_VERSION 10
+#define JM_ABI_VERSION 11
 
 #ifdef JM_SPLIT_CONSTRAINT
 // the constraint-model kernel is instantiated by jm_lib_constraint.cpp (compiled in parallel)
@@ -133,6 +133,10 @@ struct jm_batch
     int applied_k = 0;
     double applied_p[12] = {0};
     int applied_joint[4] = {1, 1, 1, 1};
+    // process forces (jm_batch_set_process_forces): spline components of the applied wrenches the kernels evaluate themselves
+    int proc_k = 0;
+    jm_process_force proc[4] = {};
+    int proc_off = 0;   // where their block (jm::ProcBlock) sits in the parameter block
     int n_cus = 256;   // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     // per-launch timing with HIP events recorded on the launch stream (bench.py roofline leg)
     bool timing = false;
@@ -143,6 +147,23 @@ struct jm_batch
 
 namespace
 {
+int32_t upload_params(jm_batch * b);
+// the description of the process forces the kernels read (jm::ProcBlock): the tail of the parameter block; pointers as bit patterns
+int32_t write_process_block(jm_batch * b)
+{
+    auto bits = [](const void * p) { double x; static_assert(sizeof(x) == sizeof(p), "64-bit pointers"); std::memcpy(&x, &p, sizeof(x)); return x; };
+    double * blk = b->params.data() + b->proc_off;
+    for (int i = 0; i < jm::JM_PROC_BLOCK; ++i) blk[i] = 0.0;
+    blk[0] = (double)b->proc_k;
+    blk[1] = bits(b->field[JM_F_LANE_TIME]);
+    for (int i = 0; i < b->proc_k; ++i)
+    {
+        double * c = blk + 2 + 6 * i;
+        c[0] = (double)b->proc[i].row; c[1] = (double)b->proc[i].n_knots; c[2] = b->proc[i].knot_spacing; c[3] = b->proc[i].scale;
+        c[4] = bits(b->proc[i].values); c[5] = bits(b->proc[i].grads);
+    }
+    return upload_params(b);
+}
 int32_t upload_params(jm_batch * b)
 {
     HIP_TRY(hipSetDevice(b->device));
@@ -206,7 +227,10 @@ template<class T> jm::BatchArgs<T> make_args(const jm_batch * b)
     A.ground_x0 = (T)b->ground_x0; A.ground_y0 = (T)b->ground_y0; A.ground_dx = (T)b->ground_dx; A.ground_dy = (T)b->ground_dy;
     A.ground_off = b->ground_h ? (const T *)b->field[JM_F_GROUND_OFFSET] : nullptr;
     A.applied = b->applied_k > 0 ? (const T *)b->field[JM_F_APPLIED] : nullptr;
-    A.applied_k = A.applied ? b->applied_k : 0;
+    // process forces: float64 tables (refused on a float32 batch by select_form), with or without held rows
+    const bool proc = b->proc_k > 0 && b->applied_k > 0 && std::is_same<T, double>::value;
+    A.applied_k = (A.applied || proc) ? b->applied_k : 0;
+    A.proc_off = proc ? b->proc_off : 0;   // (their description: the tail of the parameter block, write_process_block)
     for (int i = 0; i < 12; ++i) A.applied_p[i] = (T)b->applied_p[i];
     for (int i = 0; i < 4; ++i) A.applied_joint[i] = b->applied_joint[i];
     // spring-damper model: the lane's own friction coefficient when the field is bound (variation kernels)
@@ -230,6 +254,7 @@ template<class T> jd::Facts facts_of(const jm_batch * b, const jm::BatchArgs<T> 
     f.model_lane = A.model_lane; f.ground = A.ground_h; f.applied = A.applied; f.friction = A.friction;
     f.joint_locks = b->joint_locks; f.compact = b->ov_flags; f.B = A.B; f.n_cus = b->n_cus;
     f.torsion = b->copt.torsion >= 2.220446049250313e-16;   // (four-row contact blocks: never the fixed layout)
+    f.process = b->proc_k > 0;
     f.split = b->qcon_split; f.split_start = b->qcon_split_start; f.split_capture = b->split_capture;
     return f;
 }
@@ -426,6 +451,13 @@ template<class F> int32_t launch_as(jm_batch * b, void * stream, F && set)
 
 int32_t check_bound(const jm_batch * b, bool need_command)
 {
+    if (b->proc_k > 0)
+    {
+        if (!b->field[JM_F_LANE_TIME]) return fail(JM_ECONTROLFLOW, "process forces need the lane-time field (JM_F_LANE_TIME) bound");
+        for (int i = 0; i < b->proc_k; ++i)
+            if (b->proc[i].row >= 6 * b->applied_k)
+                return fail(JM_ECONTROLFLOW, "a process force targets a frame that jm_batch_set_applied_frames did not register");
+    }
     if (!b->field[JM_F_Q] || !b->field[JM_F_V] || !b->field[JM_F_A])
         return fail(JM_ECONTROLFLOW, "state fields q, v, a must be bound before this call");
     if (need_command && Topo::NM > 0 && !b->field[JM_F_COMMAND])
@@ -613,6 +645,8 @@ int32_t jm_batch_create(const jm_model * model, int64_t batch_size, int32_t dtyp
     b->dtype = dtype;
     b->device = device;
     b->params = model->params;
+    b->proc_off = (int)b->params.size();
+    b->params.resize(b->params.size() + jm::JM_PROC_BLOCK, 0.0);
     // kernel variant: limb-parallel when the topology allows it; JM_KERNEL_VARIANT=lane forces the
     // generic one-robot-per-lane kernel (A/B measurements)
     b->variant = (Topo::QUAD && model->root_at_origin) ? jd::FAMILY_QUAD : jd::FAMILY_LANE;
@@ -733,11 +767,30 @@ int32_t jm_batch_set_applied_frames(jm_batch * b, int32_t k, const double * offs
     for (int i = 0; i < 4; ++i) b->applied_joint[i] = (joints && i < k) ? joints[i] : 1;
     return JM_OK;
 }
+int32_t jm_batch_set_process_forces(jm_batch * b, int32_t k, const jm_process_force * forces)
+{
+    if (!b) return fail(JM_EINVAL, "jm_batch_set_process_forces: null batch");
+    if (b->started)
+        return fail(JM_ECONTROLFLOW, "A simulation is already running. Please stop it before changing the process forces.");
+    if (k < 0 || k > 4 || (k > 0 && !forces)) return fail(JM_EINVAL, "jm_batch_set_process_forces: 0 <= K <= 4 process forces");
+    for (int i = 0; i < k; ++i)
+    {
+        const jm_process_force & f = forces[i];
+        if (f.row < 0 || f.row >= 24) return fail(JM_EINVAL, "jm_batch_set_process_forces: target row out of range (6 * frame + component, 4 frames)");
+        if (f.n_knots < 1 || !(f.knot_spacing > 0.0)) return fail(JM_EINVAL, "jm_batch_set_process_forces: a process needs knots and a positive knot spacing");
+        if (!f.values || !f.grads) return fail(JM_EINVAL, "jm_batch_set_process_forces: null table");
+    }
+    if (k > 0 && b->dtype != JM_F64) return fail(JM_ENOTIMPL, "process forces need a float64 batch");
+    b->proc_k = k;
+    for (int i = 0; i < 4; ++i) b->proc[i] = i < k ? forces[i] : jm_process_force{};
+    return write_process_block(b);
+}
 int32_t jm_batch_bind(jm_batch * b, int32_t field, void * ptr)
 {
     if (!b) return fail(JM_EINVAL, "jm_batch_bind: null batch");
     if (field < 0 || field >= JM_F_COUNT) return fail(JM_ELOOKUP, "jm_batch_bind: unknown field id");
     b->field[field] = ptr;
+    if (field == JM_F_LANE_TIME && b->proc_k > 0) return write_process_block(b);
     return JM_OK;
 }
 
@@ -807,6 +860,8 @@ int32_t jm_batch_step_adaptive(jm_batch * b, double t_next, const jm_adaptive_op
     if (!b || !options) return fail(JM_EINVAL, "jm_batch_step_adaptive: null argument");
     if (!b->started)
         return fail(JM_ECONTROLFLOW, "No simulation running. Please start one before using step method.");
+    if (b->proc_k > 0)
+        return fail(JM_ENOTIMPL, "process forces are evaluated by the fixed-step kernels only: the adaptive stepper does not carry the time of its stages");
     if (!b->ad_ws || !b->ad_fs || !b->ad_is)
         return fail(JM_ECONTROLFLOW, "jm_batch_bind_adaptive must be called before the adaptive stepper is used");
     if (b->copt.contact_model == JM_CONTACT_CONSTRAINT && b->dtype != JM_F64)

@@ -1550,7 +1550,7 @@ template<class T, class Tp, class X, class SB, int CAPC, bool GEN, int PH, int I
 JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, const QConArgs<T> & C, const QStore<T> & V,
                           unsigned r, int k, const QIdx<Tp> & ix, const SB & S_, const T * qb, const T * vb, const T * ql,
                           const T * vl, const T * cmdb, const T * cmdl, bool emit, bool sensors, T * ddqb, T * ddq, int & status,
-                          int start_passes)
+                          int start_passes, T te)
 {
     using L = Layout<Tp>;
     using R = ConRows<Tp>;
@@ -1568,8 +1568,8 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
     ex.nb = R::NB;
     status &= ~JM_LANE_SOLVER_FAILURE;
     auto apply = [&]() __attribute__((always_inline)) {
-        if (emit) quad_eval<T, Tp, X, true, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, sensors, ddqb, ddq, status, &ex);
-        else quad_eval<T, Tp, X, false, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status, &ex);
+        if (emit) quad_eval<T, Tp, X, true, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, sensors, ddqb, ddq, status, &ex, nullptr, nullptr, te);
+        else quad_eval<T, Tp, X, false, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status, &ex, nullptr, nullptr, te);
     };
     if constexpr (R::NR == 0)
     {
@@ -1647,7 +1647,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
                 static_for<0, NT>([&](auto tc) { ex.tau_b[decltype(tc)::value] = uq_b[decltype(tc)::value]; });
                 ex.motors_on = true;
                 quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq,
-                                                               status, &ex, &K, &TS);
+                                                               status, &ex, &K, &TS, te);
                 if (any)
                 {
                     // (the factorisation of the streamed form's exact solve overwrote the matrix)
@@ -1659,7 +1659,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
             }
             ex.motors_on = !init;   // (first pass of Engine::start: RobotState::u is still zero)
             quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq,
-                                                           status, &ex, &K, &TS);
+                                                           status, &ex, &K, &TS, te);
             qcon_switch<T, Tp, X, GEN>(P, LT, C, B32, r32, k, ix, qb, ql, K, init, false, cx);
             any = cx.act.any();
             if (cx.overflow) status |= JM_LANE_SOLVER_FAILURE;
@@ -1728,7 +1728,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
         static_for<0, NT>([&](auto tc) { ex.tau_b[decltype(tc)::value] = uq_b[decltype(tc)::value]; });
         ex.motors_on = !(init && pass == 0);
         quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq,
-                                                       status, &ex, &K, &TS);
+                                                       status, &ex, &K, &TS, te);
         if (pass == 0)
         {
             qcon_switch<T, Tp, X, GEN>(P, LT, C, B32, r32, k, ix, qb, ql, K, init, refresh, cx);

@@ -676,17 +676,24 @@ JM_DEV void limb_unwind(const LimbTable<T> & LT, T c, T sn, M3<T> & R, V3<T> & p
 // impulse / profile forces (BatchArgs::applied: world-aligned wrenches at frames of any joint): the wrenches whose frame
 // hangs from joint `jq`, summed, as a wrench about the ROOT origin in root coordinates.  (Rj, pj) = placement of that joint in
 // root coordinates.  ≙ convertForceGlobalFrameToJoint (utilities/pinocchio.cc:794-809) followed by the joint -> root
-// transform: lin = R1^T F, ang = R1^T M + (pj + Rj p_frame) x lin.
+// transform: lin = R1^T F, ang = R1^T M + (pj + Rj p_frame) x lin.  The wrench of a frame = its held `applied` rows + its
+// process forces (BatchArgs::proc_off, ProcBlock) at the time `te` of the evaluation.
 template<class T> JM_DEV Sp<T> applied_wrench_on(const BatchArgs<T> & A, int jq, const M3<T> & R1, const M3<T> & Rj, V3<T> pj,
-                                                 unsigned B32, unsigned r32)
+                                                 unsigned B32, unsigned r32, T te)
 {
     Sp<T> f = zero6<T>();
     for (int i = 0; i < A.applied_k; ++i)
     {
         if (A.applied_joint[i] != jq) continue;
-        const unsigned o = (unsigned)(6 * i) * B32 + r32;
-        const V3<T> F = {A.applied[o], A.applied[o + B32], A.applied[o + 2 * B32]};
-        const V3<T> M = {A.applied[o + 3 * B32], A.applied[o + 4 * B32], A.applied[o + 5 * B32]};
+        V3<T> F = zero3<T>(), M = zero3<T>();
+        if (A.applied)
+        {
+            const unsigned o = (unsigned)(6 * i) * B32 + r32;
+            F = {A.applied[o], A.applied[o + B32], A.applied[o + 2 * B32]};
+            M = {A.applied[o + 3 * B32], A.applied[o + 4 * B32], A.applied[o + 5 * B32]};
+        }
+        // process forces of the frame at the time `te` of this dynamics evaluation, every lane of the quad on its own
+        if (A.proc_off > 0) add_process_forces(A, i, te, (long long)B32, (long long)r32, F, M);
         const V3<T> p = pj + Rj * V3<T>{A.applied_p[3 * i], A.applied_p[3 * i + 1], A.applied_p[3 * i + 2]};
         const V3<T> fl = tmul(R1, F);
         f.l = f.l + fl;
@@ -694,9 +701,9 @@ template<class T> JM_DEV Sp<T> applied_wrench_on(const BatchArgs<T> & A, int jq,
     }
     return f;
 }
-template<class T> JM_DEV Sp<T> applied_root_wrench(const BatchArgs<T> & A, const M3<T> & R1, unsigned B32, unsigned r32)
+template<class T> JM_DEV Sp<T> applied_root_wrench(const BatchArgs<T> & A, const M3<T> & R1, unsigned B32, unsigned r32, T te)
 {
-    return applied_wrench_on(A, 1, R1, ident3<T>(), zero3<T>(), B32, r32);
+    return applied_wrench_on(A, 1, R1, ident3<T>(), zero3<T>(), B32, r32, te);
 }
 // a wrench about the root origin (root coordinates) expressed in the frame of a joint placed at (Rj, pj)
 template<class T> JM_DEV Sp<T> wrench_to_joint(const M3<T> & Rj, V3<T> pj, Sp<T> w)
@@ -751,8 +758,9 @@ template<class T, class Tp, class X, bool EMIT, class SB, int CFM = 0, class KEE
 JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, unsigned r, int k, const QIdx<Tp> & ix,
                       const SB & S_, const T * qb, const T * vb_, const T * ql, const T * vl_, const T * cmdb_, const T * cmdl_,
                       bool sensors, T * ddqb, T * ddq, int & status, const QExtra<T, Tp> * ex = nullptr, KEEP * keep = nullptr,
-                      TrunkStore<T, Tp> * ts_out = nullptr)
+                      TrunkStore<T, Tp> * ts_out = nullptr, T te = T(0))
 {
+    (void)te;   // time of this dynamics evaluation: read by the process forces (GEN)
     // velocities / commands: registers for short limbs, re-read from the stage buffer for long ones
     using RW = QRows<Tp>;
     auto vlq = [&](int s) -> T { if constexpr (RW::LONG) return S_.getl(RW::KVL + s); else return vl_[s]; };
@@ -961,7 +969,7 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
                     put6(A.f_external, B32, r32, 0, zero6<T>());
                     static_for<0, NT>([&](auto tc) { put6(A.f_external, B32, r32, 6 * Tp::trunk_joint[decltype(tc)::value], zero6<T>()); });
                     if constexpr (GEN)
-                        if (A.applied_k > 0) put6(A.f_external, B32, r32, 6 * Tp::trunk_joint[0], applied_root_wrench(A, R1, Bg, rg));
+                        if (A.applied_k > 0) put6(A.f_external, B32, r32, 6 * Tp::trunk_joint[0], applied_root_wrench(A, R1, Bg, rg, te));
                 }
                 static_for<0, N>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
@@ -1074,7 +1082,7 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
             if constexpr (GEN)
                 if (A.applied_k > 0)
                 {
-                    const Sp<T> w = applied_wrench_on(A, limb_joint_of(sc), R1, Rcur, pcur, Bg, rg);
+                    const Sp<T> w = applied_wrench_on(A, limb_joint_of(sc), R1, Rcur, pcur, Bg, rg, te);
                     f = f - w;
                     if constexpr (EMIT)   // (evaluations that emit their own outputs: the constraint contact model)
                         if (A.f_external && ix.has[s]) add6(A.f_external, B32, r32, 6u * (unsigned)limb_joint_of(sc), wrench_to_joint(Rcur, pcur, w));
@@ -1148,7 +1156,7 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
         if constexpr (GEN)
             if (A.applied_k > 0)
             {
-                const Sp<T> w = applied_wrench_on(A, j, R1, Xt.R, Xt.p, Bg, rg);
+                const Sp<T> w = applied_wrench_on(A, j, R1, Xt.R, Xt.p, Bg, rg, te);
                 f = f - w;
                 if constexpr (EMIT)
                     if (A.f_external && lead) put6(A.f_external, B32, r32, 6 * j, wrench_to_joint(Xt.R, Xt.p, w));
@@ -1186,7 +1194,7 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
         Sp<T> f1 = cross_mf(v1r, rbi_mul(Y1, v1r));
         if constexpr (I::has_child(0)) { I1 = I1 + accA[0]; f1 = f1 + accF[0]; }
         if constexpr (GEN)
-            if (A.applied_k > 0) f1 = f1 - applied_root_wrench(A, R1, Bg, rg);   // impulse / profile forces on the root body
+            if (A.applied_k > 0) f1 = f1 - applied_root_wrench(A, R1, Bg, rg, te);   // impulse / profile forces on the root body
         const Sp<T> Ya = ai_mul(I1, agf1);
         T b[6] = {-f1.l.x - Ya.l.x, -f1.l.y - Ya.l.y, -f1.l.z - Ya.l.z, -f1.a.x - Ya.a.x, -f1.a.y - Ya.a.y, -f1.a.z - Ya.a.z};
         T M[6][6];
@@ -1385,7 +1393,7 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
                     if constexpr (GEN)
                         if (A.applied_k > 0)
                         {
-                            const Sp<T> w = applied_wrench_on(A, limb_joint_of(sc), R1, Rcur, pcur, Bg, rg);
+                            const Sp<T> w = applied_wrench_on(A, limb_joint_of(sc), R1, Rcur, pcur, Bg, rg, te);
                             fjs = fjs - w;
                             fxs = fxs + w;
                             if (applied_out && ix.has[s]) add6(A.f_external, B32, r32, 6u * (unsigned)limb_joint_of(sc), wrench_to_joint(Rcur, pcur, w));
@@ -1438,10 +1446,10 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
                     if (A.applied_k > 0)
                     {
                         Sp<T> w;
-                        if constexpr (t == 0) w = applied_root_wrench(A, R1, Bg, rg);
+                        if constexpr (t == 0) w = applied_root_wrench(A, R1, Bg, rg, te);
                         else
                         {
-                            w = applied_wrench_on(A, j, R1, Xt.R, Xt.p, Bg, rg);
+                            w = applied_wrench_on(A, j, R1, Xt.R, Xt.p, Bg, rg, te);
                             if (applied_out && lead) put6(A.f_external, B32, r32, 6 * j, wrench_to_joint(Xt.R, Xt.p, w));
                         }
                         fjT[t] = fjT[t] - w;
@@ -1507,8 +1515,9 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
 template<class T, class Tp, class X, int CFM = 0, bool GEN = false>
 JM_DEV void quad_extra_terms(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, unsigned r32, int k, const QIdx<Tp> & ix,
                              const T * qb, const T * vb, const T * ql, const T * vl, const T * ddqb, const T * ddq,
-                             const QExtra<T, Tp> * ex = nullptr)
+                             const QExtra<T, Tp> * ex = nullptr, T te = T(0))
 {
+    (void)te;
     using L = Layout<Tp>;
     using Q = QLayout<Tp>;
     using I = QInfo<Tp>;
@@ -1635,7 +1644,7 @@ JM_DEV void quad_extra_terms(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs
             if constexpr (GEN)
                 if (A.applied_k > 0)
                     fjs = fjs - applied_wrench_on(A, sel4(k, Tp::limb_joint[0][s], Tp::limb_joint[1][s], Tp::limb_joint[2][s], Tp::limb_joint[3][s]),
-                                                  R1, Rs[s], ps[s], Bg, rg);
+                                                  R1, Rs[s], ps[s], Bg, rg, te);
             ms += Y.m;
             mcs = mcs + Y.m * Y.c;
             if (A.joint_forces && ix.has[s])
@@ -1679,8 +1688,8 @@ JM_DEV void quad_extra_terms(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs
         if constexpr (GEN)
             if (A.applied_k > 0)
             {
-                if constexpr (t == 0) fjT[0] = fjT[0] - applied_root_wrench(A, R1, Bg, rg);
-                else fjT[t] = fjT[t] - applied_wrench_on(A, j, R1, K.X[t].R, K.X[t].p, Bg, rg);
+                if constexpr (t == 0) fjT[0] = fjT[0] - applied_root_wrench(A, R1, Bg, rg, te);
+                else fjT[t] = fjT[t] - applied_wrench_on(A, j, R1, K.X[t].R, K.X[t].p, Bg, rg, te);
             }
         mT[t] += Y.m;
         mcT[t] = mcT[t] + Y.m * Y.c;
@@ -1743,7 +1752,7 @@ template<class T, class Tp, class X, class SB, int CAPC, bool GEN, int PH = 0, i
 JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, const QConArgs<T> & C, const QStore<T> & V,
                           unsigned r, int k, const QIdx<Tp> & ix, const SB & S_, const T * qb, const T * vb, const T * ql,
                           const T * vl, const T * cmdb, const T * cmdl, bool emit, bool sensors, T * ddqb, T * ddq, int & status,
-                          int start_passes);
+                          int start_passes, T te = T(0));
 
 // one lane of a quad: robot r, limb k. `S` = stage buffer views of this lane.  QCON: every evaluation is the
 // constrained one (`C` / `V`: constraint state and the robot's solver region).
@@ -1801,6 +1810,26 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
     const bool rk4 = A.solver == JM_SOLVER_RUNGE_KUTTA_4;
     const int pre = stepping ? (A.command_changed ? 1 : 0) : 1;
     const int n_evals = stepping ? pre + A.n_sub * (rk4 ? 4 : 1) : 1;
+    // process forces (GEN, never the split forms): `tl` = the robot's time at the start of the integrator step (JM_F_LANE_TIME;
+    // 0 at `start` and for the robots of a reset), `te` = time of the evaluation about to run.  Each of the four lanes keeps
+    // its own copy; the lead lane stores it.
+    T tl = T(0), te = T(0);
+    (void)tl;
+    if constexpr (GEN && PH == 0)
+        if (A.proc_off > 0)
+        {
+            if (A.mode == MODE_START || A.mode == MODE_RESET) { if (lead) proc_block(A).lane_time()[r32] = T(0); }
+            else tl = proc_block(A).lane_time()[r32];
+            te = tl;
+        }
+    // evaluation time of stage `st` (abstract_runge_kutta_stepper.cc:33-73, c = 1/2 1/2 1; euler_explicit_stepper.cc:5-21)
+    auto stage_time = [&](int st) {
+        if constexpr (GEN && PH == 0)
+        {
+            if (st == 3) tl = tl + dt;
+            te = (st == -1 || st == 3) ? tl : tl + (st == 2 ? dt : dt * T(0.5));
+        }
+    };
     // Stage-buffer invariant at the start of every integrator step: q0/v0 = state, kv = v0,
     // accumulators = 0, ddq(b) registers = a(state).  Every stage update is then the same
     // straight-line code (no per-element `first stage ?` branches around the LDS reads).
@@ -2016,9 +2045,10 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
             rr = r32;
             JM_OPAQUE(rr);
             advance(st, last, rr);
+            if (stepping) stage_time(st);
             quad_eval_con<T, Tp, X, StageBuf<T, SL, SB>, CAPC, GEN, 0, INIT>(P, LT, A, *C, *V, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, last && A.mode != MODE_DYNAMICS,
                                     (!stepping && A.mode != MODE_REFRESH) || A.update_sensors != 0, ddqb, ddq, status,
-                                    start_passes);
+                                    start_passes, te);
         }
         }
     }
@@ -2045,7 +2075,9 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
             CPtr<T> Pl = P;
             if constexpr (R::LONG && !GEN) JM_OPAQUE_S(Pl);
             advance(st, e == n_evals - 1, rr);
-            quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(Pl, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status);
+            stage_time(st);
+            quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(Pl, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status,
+                                                                             nullptr, nullptr, nullptr, te);
         }
     }
     else
@@ -2054,7 +2086,8 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         rr = r32;
         JM_OPAQUE(rr);
         advance(-1, true, rr);
-        quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status);
+        quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status,
+                                                                         nullptr, nullptr, nullptr, te);
     }
     if (A.mode != MODE_DYNAMICS)
     {
@@ -2067,7 +2100,8 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         static_for<0, NVB>([&](auto ic) { vb[decltype(ic)::value] = S.getb(R::V0B + decltype(ic)::value); });
         static_for<0, N>([&](auto sc) { ql[decltype(sc)::value] = S.getl(R::Q0L + decltype(sc)::value); vl[decltype(sc)::value] = S.getl(R::V0L + decltype(sc)::value); });
         quad_eval<T, Tp, X, true, StageBuf<T, SL, SB>, 0, NoKeep, GEN, false>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl,
-                                  (!stepping && A.mode != MODE_REFRESH) || A.update_sensors != 0, ddqb, ddq, status);
+                                  (!stepping && A.mode != MODE_REFRESH) || A.update_sensors != 0, ddqb, ddq, status,
+                                  nullptr, nullptr, nullptr, te);
     }
     }
     {
@@ -2078,6 +2112,8 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         {
             const int stq = X::quad_or(status);
             if (A.status && lead) A.status[rr] = (A.mode == MODE_REFRESH) ? (A.status[rr] | stq) : stq;
+            if constexpr (GEN && PH == 0)
+                if (stepping && lead && A.proc_off > 0) proc_block(A).lane_time()[rr] = tl;
             // (spring-damper kernels: the output pass above has written the extra terms already)
             if constexpr (QCON)
             if (A.joint_forces || A.centroidal)
@@ -2091,7 +2127,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
                 ex.flags = C->flags;
                 ex.nb = qcon_first_contact_row<Tp>();
                 ex.lam = C->data + (size_t)qcon_first_lambda_row<Tp>() * B32;
-                quad_extra_terms<T, Tp, X, 2, GEN>(P, LT, A, rr, k, ix, qb, vb, ql, vl, ddqb, ddq, &ex);
+                quad_extra_terms<T, Tp, X, 2, GEN>(P, LT, A, rr, k, ix, qb, vb, ql, vl, ddqb, ddq, &ex, te);
             }
         }
     }

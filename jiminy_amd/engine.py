@@ -134,6 +134,28 @@ def impulse_active(t_impulse: float, dt_impulse: float, t: float, was_active: bo
     return active
 
 
+_PROCESS_FORCE_ADAPTIVE = ("process forces are evaluated by the fixed-step kernels ('euler_explicit', 'runge_kutta_4'): "
+                           "the adaptive stepper does not carry the time of its stages to them")
+
+
+def launch_pieces(n: int, sensors: bool, per_step_noise: bool, profile_forces: Any, process_forces: Any = ()) -> List[int]:
+    """Integrator steps of every launch that runs the `n` steps of one interval of `plan_step`.  One launch, unless
+    something on the host has to happen between the steps: noise drawn after every step of a continuous sensor refresh,
+    or a callable profile force of update period 0, re-evaluated at the start of every step.  `process_forces` are
+    evaluated by the kernels themselves and never cut a launch."""
+    del process_forces
+    per_step_forces = any(p["period"] <= EPS for p in profile_forces)
+    return [1] * n if ((per_step_noise and sensors) or per_step_forces) else [n]
+
+
+def refresh_needed(cmd_breakpoint: bool, piece: int, command_dirty: bool, constraint_model: bool, held_forces_changed: bool) -> bool:
+    """`command_changed` of a launch: the a(t+) refresh at a controller breakpoint (engine.cc:2030-2042) -- skipped when
+    the held command was not rewritten (the evaluation is idempotent), except with the constraint contact model, where the
+    reference's refresh re-runs the warm-started PGS solve -- and whenever a HELD applied force changed at the start of
+    the launch (`_update_applied_forces`; process forces are part of the dynamics and never count)."""
+    return bool((cmd_breakpoint and (command_dirty or constraint_model) and piece == 0) or held_forces_changed)
+
+
 def min_clipped(*values: float) -> float:
     """≙ `minClipped` (utilities/helpers.hxx:59-92): the smallest of the values that exceed EPS, INF when there is none."""
     valid = [float(v) for v in values if float(v) > EPS]
@@ -872,6 +894,8 @@ class BatchedEngine:
         self._impulse_forces: List[Dict[str, Any]] = []
         self._impulse_active: List[int] = []
         self._profile_forces: List[Dict[str, Any]] = []
+        self._process_forces: List[Dict[str, Any]] = []
+        self._applied_clean = False   # the `applied` rows are known to be zero (nothing held is registered)
         self._apply_options()
         self._apply_hardware_sensor_options()
 
@@ -1381,6 +1405,8 @@ class BatchedEngine:
         for pf in self._profile_forces:
             pf["value"], pf["t_last"] = None, -math.inf
         self._impulse_active = []
+        if self._process_forces and self._options["stepper"]["odeSolver"] == "runge_kutta_dopri":
+            raise NotImplementedError(_PROCESS_FORCE_ADAPTIVE)
         self._update_applied_forces(0.0)
         self._check_variation_kernels()
         self._lib.check(self._L.jm_batch_start(self._batch_h, self._stream()))
@@ -1514,20 +1540,17 @@ class BatchedEngine:
         # continuous profile forces (update_period = 0) are functions of (t, q, v): the reference evaluates them inside
         # every dynamics evaluation (computeExternalForces, engine.cc:3481-3492).  Here they are re-evaluated at the
         # start of every integrator step (launches cut to one step): piecewise constant over dtMax at most.
-        per_step_forces = any(p["period"] <= EPS for p in self._profile_forces)
+        # Process forces (`register_process_force`) are evaluated by the kernels inside every evaluation, at its own
+        # time: part of the dynamics, neither a cut nor a changed input (`launch_pieces`, `refresh_needed`).
         # (only discrete controllers have breakpoints: engine.cc:1919-1940)
         constraint_model = (self._options["contacts"]["model"] == "constraint"
                             and float(self._options["stepper"]["controllerUpdatePeriod"]) > EPS)
         t_now = self._t
         for dt, n, cmd_bp, sens in launches:
-            for k, n_k in enumerate([1] * n if ((per_step_noise and sens) or per_step_forces) else [n]):
+            for k, n_k in enumerate(launch_pieces(n, sens, per_step_noise, self._profile_forces, self._process_forces)):
                 forces_changed = self._update_applied_forces(t_now)
                 t_now += dt * n_k
-                # a(t+) refresh at a controller breakpoint (engine.cc:2030-2042): skipped when the held
-                # command was not rewritten (the evaluation is idempotent) -- except with the constraint
-                # contact model, where the reference's refresh re-runs the warm-started PGS solve; and whenever
-                # an applied force changed at the start of this launch
-                changed = (cmd_bp and (self._command_dirty or constraint_model) and k == 0) or forces_changed
+                changed = refresh_needed(cmd_bp, k, self._command_dirty, constraint_model, forces_changed)
                 self._lib.check(self._L.jm_batch_step(self._batch_h, solver, dt, n_k, int(changed),
                                                       int(sens), stream))
                 if changed and cmd_bp:
@@ -1833,10 +1856,66 @@ class BatchedEngine:
         self._profile_forces.append({"frame": self._force_frame_index(frame_name), "func": func,
                                      "period": float(update_period), "t_last": -math.inf, "value": None})
 
+    def register_process_force(self, frame_name: str, process: Any, component: int, scale: float = 1.0) -> None:
+        """A continuous profile force the DEVICE evaluates: component `component` (0..2 force x y z, 3..5 moment, world
+        aligned) of the wrench on `frame_name` is `scale * process(lane time)`, added to the held impulse / profile value
+        of that frame.  `process` is a `PeriodicGaussianProcess` (or Fourier) of this batch size on this device; its
+        `values` / `grads` tables are read in place by the kernels inside EVERY dynamics evaluation, at the time of the
+        evaluation -- what `Engine::computeExternalForces` does with a profile force of update period 0
+        (engine.cc:3482-3494) -- so `process.reset(...)` between launches takes effect without a new registration.
+        Lane time (`lane_time`) is 0 at `start` and for the lanes of `reset_lanes`, and advances with every integrator
+        step.  Such forces neither cut launches nor force an a(t+) refresh.  At most 4 components; fixed-step solvers."""
+        if self._running:
+            raise BadControlFlow("Simulation already running. Please stop it before registering new forces.")
+        if self._options["stepper"]["odeSolver"] == "runge_kutta_dopri":
+            raise NotImplementedError(_PROCESS_FORCE_ADAPTIVE)
+        if len(self._process_forces) >= 4:
+            raise ValueError("at most 4 process force components can be registered")
+        if not 0 <= int(component) < 6:
+            raise ValueError("component must be in 0..5 (force x y z, moment x y z)")
+        values, grads = getattr(process, "values", None), getattr(process, "grads", None)
+        if not isinstance(values, torch.Tensor) or not isinstance(grads, torch.Tensor):
+            raise ValueError("process must carry `values` and `grads` tables (PeriodicGaussianProcess)")
+        n = int(process.num_times)
+        if tuple(values.shape) != (n, self.batch_size) or tuple(grads.shape) != (n, self.batch_size):
+            raise ValueError(f"the process has batch size {values.shape[-1]}, the engine {self.batch_size}")
+        if values.device != self.device or grads.device != self.device:
+            raise ValueError(f"the process lives on {values.device}, the engine on {self.device}")
+        if values.dtype != torch.float64 or grads.dtype != torch.float64 or not values.is_contiguous() or not grads.is_contiguous():
+            raise ValueError("the process tables must be contiguous float64 tensors")
+        frame = self._force_frame_index(frame_name)
+        self._process_forces.append({"frame": frame, "component": int(component), "scale": float(scale), "process": process})
+        try:
+            self._set_process_forces()
+        except Exception:
+            self._process_forces.pop()
+            raise
+
+    def _set_process_forces(self) -> None:
+        k = len(self._process_forces)
+        if k and "lane_time" not in self._fields:
+            self._fields["lane_time"] = torch.zeros((1, self.batch_size), dtype=torch.float64, device=self.device)
+            self._bind("lane_time")
+        arr = (_abi.ProcessForce * max(k, 1))()
+        for i, f in enumerate(self._process_forces):
+            p = f["process"]
+            arr[i] = _abi.ProcessForce(6 * f["frame"] + f["component"], int(p.num_times), float(p.dt), f["scale"],
+                                       p.values.data_ptr(), p.grads.data_ptr())
+        self._lib.check(self._L.jm_batch_set_process_forces(self._batch_h, k, arr if k else None))
+
+    @property
+    def lane_time(self) -> torch.Tensor:
+        """`(B,)` float64: the time of every lane as the kernels keep it while process forces are registered."""
+        if "lane_time" not in self._fields:
+            raise LookupError("lane time is kept while process forces are registered (register_process_force)")
+        return self._fields["lane_time"][0]
+
     def remove_all_forces(self) -> None:
         """≙ `Engine.remove_all_forces` (engine.cc:1937-1960)."""
         if self._running:
             raise BadControlFlow("Simulation already running. Please stop it before removing forces.")
+        self._process_forces.clear()
+        self._set_process_forces()
         self._impulse_forces.clear()
         self._impulse_active = []
         self._profile_forces.clear()
@@ -1868,6 +1947,13 @@ class BatchedEngine:
         if "applied" not in self._fields:
             return False
         a = self._fields["applied"]
+        if not (self._impulse_forces or self._impulse_active or self._profile_forces):
+            # nothing held (process forces only): the rows stay zero, no tensor program per launch
+            if not self._applied_clean:
+                a.zero_()
+                self._applied_clean = True
+            return False
+        self._applied_clean = False
         a.zero_()
         active = []
         changed = False

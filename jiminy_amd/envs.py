@@ -43,8 +43,16 @@ class VecJiminyEnv:
                  std_ratio: Optional[Dict[str, float]] = None,
                  model_options: Optional[Dict[str, Dict[str, float]]] = None,
                  ground_profile: Optional[Tuple[Any, Tuple[float, float], Tuple[float, float], float]] = None,
-                 ground_patch_extent: Optional[Tuple[float, float]] = None) -> None:
+                 ground_patch_extent: Optional[Tuple[float, float]] = None,
+                 disturbance_on_device: bool = False, disturbance_impulses: bool = True) -> None:
         self.model = model
+        # the continuous disturbance force (std_ratio['disturbance']) as PROCESS FORCES: the step kernels evaluate the two
+        # Gaussian processes inside every dynamics evaluation, at its own time, like the reference's profile force
+        # (`BatchedEngine.register_process_force`) -- instead of a callable the host re-evaluates at the start of every
+        # integrator step.  `disturbance_impulses=False` keeps only that continuous part: nothing is scheduled on the
+        # host any more, and the step can be replayed as a graph (`enable_graph`).
+        self._disturbance_on_device = bool(disturbance_on_device)
+        self._disturbance_impulses = bool(disturbance_impulses)
         # every environment its own patch of the ground profile: at every (lane) reset a new (x, y) offset of its
         # height-map queries, uniform in +- extent (`BatchedEngine.set_ground_offsets`) -- the batched form of a new random
         # `groundProfile` per environment instance and episode
@@ -344,7 +352,7 @@ class VecJiminyEnv:
         g = self._generator
         B = self.num_envs
         self.engine._force_frame_index(frame)    # binds the `applied` field while no simulation is running
-        self._impulse_frame = frame
+        self._impulse_frame = frame if self._disturbance_impulses else None
         self._impulse_index = 1                  # the push of period k starts at k * F_IMPULSE_PERIOD +- delta
         self._impulse_end = 0.0
         # the continuous part (envs/locomotion.py:165-167, 327-359): two periodic Gaussian processes, one realisation
@@ -356,6 +364,11 @@ class VecJiminyEnv:
         self._dev_gen = None          # re-seeded from the (just re-seeded) host generator at its next use
         for proc in self._f_xy_profile:
             proc.reset(g)
+        if self._disturbance_on_device:
+            # lane time (0 at `start` and for the lanes of `reset_lanes`) is the episode time of every environment
+            for component, proc in enumerate(self._f_xy_profile):
+                self.engine.register_process_force(frame, proc, component, self.F_PROFILE_SCALE * scale)
+            return
 
         def profile(t: float, q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
             w = torch.zeros((6, B), dtype=self.dtype, device=self.device)
@@ -619,8 +632,10 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
         launch -> Mahony filter: 26 launches for ANYmal -- as ONE captured HIP graph instead of issuing them from
         Python.  For small batches per GPU (a sharded config 4 / 5: a few thousand environments) the step is bound by
         the host's launch rate, not by the kernels; at B = 65 536 it makes no difference.  Needs the HIP blocks, a
-        fixed-step solver, no sensor noise / delay and no applied forces (their host-side schedules run between the
-        launches).  The graph is captured at the next `step` and dropped by `reset`.
+        fixed-step solver, no sensor noise / delay and no applied forces whose schedule runs on the host between the
+        launches: impulses and callable profiles.  Process forces (`disturbance_on_device=True` with
+        `disturbance_impulses=False`) are part of the captured kernels -- they read the lane time and the process tables
+        from device memory -- and replay like the rest.  The graph is captured at the next `step` and dropped by `reset`.
 
         `whole_step=True` captures the WHOLE `env.step`: the physics chain, the episode clock, termination / truncation,
         the reward and an unconditional masked auto-reset (`reset_lanes` with the `done` mask: lanes that are not done
@@ -633,10 +648,13 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
             if self._hip_blocks is None or eng._adaptive is not None or eng._sensor_noise or eng._impulse_forces or eng._profile_forces \
                     or getattr(self, "_impulse_frame", None) is not None:
                 raise NotImplementedError("enable_graph needs the HIP blocks, a fixed-step solver, noiseless sensors and "
-                                          "no applied forces")
+                                          "no applied forces but process forces (disturbance_on_device=True, "
+                                          "disturbance_impulses=False)")
             if whole_step and (not self.auto_reset or float(self.std_ratio.get("ground", 0.0)) > 0.0 or
                                self._ground_patch_extent is not None):
                 raise NotImplementedError("whole-step graphs need auto_reset and no ground-friction / terrain-patch randomisation")
+            if whole_step and (eng._process_forces or float(self.std_ratio.get("disturbance", 0.0)) > 0.0):
+                raise NotImplementedError("whole-step graphs take no disturbance: their reset draws new realisations")
         self._graph_enabled = bool(enable)
         self._graph_whole = bool(enable and whole_step)
         self._graph = None
@@ -650,7 +668,10 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
         if eng._adaptive is not None or eng._sensor_noise or eng._impulse_forces or eng._profile_forces \
                 or getattr(self, "_impulse_frame", None) is not None:
             raise NotImplementedError("enable_graph needs a fixed-step solver, noiseless sensors and no applied forces "
-                                      "(std_ratio['disturbance'] registers forces at reset())")
+                                      "but process forces (std_ratio['disturbance'] registers forces at reset(): "
+                                      "disturbance_on_device=True, disturbance_impulses=False keeps them on the device)")
+        if self._graph_whole and eng._process_forces:
+            raise NotImplementedError("whole-step graphs take no disturbance: their reset draws new realisations")
         if self._graph_whole:
             a, b = self._sample_state(self.num_envs), self._sample_state(self.num_envs)
             if not (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])):

@@ -1,0 +1,83 @@
+#!/usr/bin/env python
+"""Cost of the continuous disturbance force of the ANYmal PD environment, host callable against process forces.
+    python tools/bench_process_force.py [--envs 65536 4096] [--steps 200] [--warmup 10] [--repeats 3] [--root CHECKOUT]
+One environment step (`make_anymal_env`, PD pipeline) in every combination of
+  * B = `--envs`;
+  * explicit Euler with the shipped periods (dtMax 1e-3, controller 5 ms), and RK4 at dtMax 1e-3;
+  * spring-damper and constraint contact model;
+  * legs: `undisturbed`; `callable` = std_ratio['disturbance'] through the host callable (re-evaluated at the start of every
+    integrator step, launches cut to one step, an a(t+) refresh per launch); `process` = the same disturbance with the two
+    Gaussian processes registered as process forces (`disturbance_on_device=True`: evaluated by the kernels); `process_graph` =
+    the continuous part alone (`disturbance_impulses=False`) replayed as a captured graph.
+Device-synchronised wall time over `--steps` environment steps after `--warmup`, `--repeats` times per leg with the legs
+alternating; prints one JSON line with the median and the spread (max - min) of every leg in ms per environment step.
+`--root` imports the package from another checkout (an older commit has no `process` legs: they are skipped), so that two
+commits can be timed in one session:  --legs callable --root ../parent."""
+import argparse
+import inspect
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, nargs="+", default=[65536, 4096])
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--legs", nargs="+", default=["undisturbed", "callable", "process", "process_graph"])
+    ap.add_argument("--solvers", nargs="+", default=["euler_explicit", "runge_kutta_4"])
+    ap.add_argument("--contact-models", nargs="+", default=["spring_damper", "constraint"])
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    from jiminy_amd.envs import VecJiminyEnv, make_anymal_env
+    on_device = "disturbance_on_device" in inspect.signature(VecJiminyEnv.__init__).parameters
+    legs = [leg for leg in args.legs if on_device or not leg.startswith("process")]
+    dev = torch.device("cuda", 0)
+    leg_kw = {"undisturbed": {},
+              "callable": {"std_ratio": {"disturbance": 0.3}},
+              "process": {"std_ratio": {"disturbance": 0.3}, "disturbance_on_device": True},
+              "process_graph": {"std_ratio": {"disturbance": 0.3}, "disturbance_on_device": True, "disturbance_impulses": False}}
+    out = {"metric": "ANYmal PD environment step under the continuous disturbance, ms", "root": os.path.abspath(args.root),
+           "steps": args.steps, "repeats": args.repeats, "results": []}
+    for B in args.envs:
+        action = torch.zeros((B, 12), dtype=torch.float64, device=dev)
+        for solver in args.solvers:
+            for contact_model in args.contact_models:
+                envs = {}
+                for leg in legs:
+                    env = make_anymal_env(B, device=dev, ode_solver=solver, dt_max=1e-3, contact_model=contact_model, **leg_kw[leg])
+                    if leg == "process_graph":
+                        env.enable_graph()
+                    env.reset(seed=0)
+                    for _ in range(args.warmup):
+                        env.step(action)
+                    envs[leg] = env
+                times = {leg: [] for leg in legs}
+                for _ in range(args.repeats):
+                    for leg in legs:          # alternating legs: drift of the machine hits all of them alike
+                        env = envs[leg]
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(args.steps):
+                            env.step(action)
+                        torch.cuda.synchronize()
+                        times[leg].append(1e3 * (time.perf_counter() - t0) / args.steps)
+                row = {"envs": B, "solver": solver, "contact_model": contact_model}
+                for leg in legs:
+                    row[leg] = {"median_ms": round(statistics.median(times[leg]), 4),
+                                "spread_ms": round(max(times[leg]) - min(times[leg]), 4)}
+                out["results"].append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                del envs
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
