@@ -327,13 +327,14 @@ int32_t jm_batch_set_applied_frames(jm_batch * batch, int32_t k, const double * 
 /* Process forces (ABI 11): wrench components that are a function of time, evaluated by the kernels inside EVERY dynamics
  * evaluation at the time of that evaluation, the way Engine::computeExternalForces calls a profile force
  * (core/src/engine/engine.cc:3482-3494) -- a(t+) refresh at t, RK4 stages at t + dt/2, t + dt/2, t + dt, the end-of-step
- * evaluation of either solver at t + dt (abstract_runge_kutta_stepper.cc:33-73, euler_explicit_stepper.cc:5-21), `start`,
- * `reset_lanes` and `dynamics` at the lane's current time; t = JM_F_LANE_TIME.  Component `row % 6` (force x y z, moment x y z,
+ * evaluation of either solver at t + dt (abstract_runge_kutta_stepper.cc:33-73, euler_explicit_stepper.cc:5-21), stage i of an
+ * attempt of size dt of the adaptive stepper at t + c_i dt, c = 1/5, 3/10, 4/5, 8/9, 1, 1 (runge_kutta_dopri_stepper.h:21-23;
+ * jm_batch_step_adaptive), `start`, `reset_lanes` and `dynamics` at the lane's current time; t = JM_F_LANE_TIME.  Component `row % 6` (force x y z, moment x y z,
  * world aligned) of frame `row / 6` of jm_batch_set_applied_frames is its JM_F_APPLIED value (zero when that field is unbound)
  * plus `scale * p(t)`, p the periodic cubic Hermite spline of PeriodicGaussianProcess (core/src/utilities/random.cc:322-458)
  * through `n_knots` knots `knot_spacing` apart: `values`, `grads` = device arrays `[n_knots][B]` of float64, one realisation
  * per lane, read at every evaluation (the caller may refill them in place between launches).  K <= 4, K = 0 disables; refused
- * while a simulation is running, on float32 batches and by the adaptive stepper. */
+ * while a simulation is running and on float32 batches. */
 typedef struct jm_process_force {
     int32_t row;            /* 6 * frame + component */
     int32_t n_knots;
@@ -388,6 +389,10 @@ int32_t jm_batch_timing_summary(jm_batch * batch, int32_t * n_launches, double *
  * call (resets the successive-failure counters, clears the status row).  Lanes whose step size falls
  * below 1e-10 s or that fail more than `successive_iter_failed_max` times in a row get
  * JM_LANE_STEPPER_FAILURE (the reference raises for its single robot, engine.cc:2340-2384).
+ * Process forces (jm_batch_set_process_forces) are evaluated at the time of every stage, lane time + c_i dt_try, in both forms
+ * of the stepper; an accepted step advances JM_F_LANE_TIME by its size as it advances `t`, a rejected one leaves it; the a(t+)
+ * refresh (`command_changed`) and the closing refresh evaluate at lane time.  The row the per-stage form keeps the stage times
+ * in belongs to the library (allocated by jm_batch_bind_adaptive).
  * The call synchronises the stream once per attempt (active-lane count); `attempts_out` (optional)
  * receives the number of attempts, `max_attempts` bounds it. */
 typedef struct jm_adaptive_options

@@ -41,7 +41,14 @@ JM_TABLEAU double A[7][7] = {
     {35.0 / 384.0, 0.0, 500.0 / 1113.0, 125.0 / 192.0, -2187.0 / 6784.0, 11.0 / 84.0, 0}};
 JM_TABLEAU double E[7] = {5179.0 / 57600.0, 0.0, 7571.0 / 16695.0, 393.0 / 640.0, -92097.0 / 339200.0,
                                              187.0 / 2100.0, 1.0 / 40.0};
+// nodes: stage i = 1..6 is evaluated at t + C[i] dt (runge_kutta_dopri_stepper.h:21-23; abstract_runge_kutta_stepper.cc:46,
+// f(t + c_[i] * dt, .)); index 0 = k_0, the derivative carried over from the previous step (FSAL)
+JM_TABLEAU double C[7] = {0.0, 1.0 / 5.0, 3.0 / 10.0, 4.0 / 5.0, 8.0 / 9.0, 1.0, 1.0};
 constexpr double STEPPER_ORDER = 5.0, SAFETY = 0.8, ERROR_THRESHOLD = 0.5, MIN_FACTOR = 0.2, MAX_FACTOR = 5.0;
+// Time of stage `i` (1..6) of an attempt of size `dt` by a lane whose process time is `tl`: what the process forces of that
+// evaluation are read at, in both forms of the stepper (k_dopri_stage here, quad_dopri_run in jm_qdopri.h).  Stage 6 is the
+// solution at tl + dt: its acceleration stays valid as k_0 of the next step under a time-dependent force.
+JM_DEV double stage_time(double tl, int i, double dt) { return tl + C[i] * dt; }
 }
 constexpr double STEPPER_MIN_TIMESTEP = 1e-10, SIMULATION_MIN_TIMESTEP = 1e-6;
 
@@ -68,6 +75,10 @@ template<class T> struct AdaptiveArgs
     long long B;
     double t_next, tol_rel, tol_abs, dt_max, dt_restore_threshold_rel;
     int succ_failed_max, new_step, stage;
+    // process forces (per-stage form; null without them): the lanes' process time `[1][B]` (JM_F_LANE_TIME, advanced by the
+    // finish kernel with AD_T) and the library-owned row `[B]` the stage kernel leaves the time of the coming evaluation in,
+    // both in batch order (ProcBlock::stage_time)
+    T * lane_time; double * stage_time;
 };
 template<class Tp> struct AdaptiveRows
 {
@@ -209,6 +220,7 @@ __global__ void __launch_bounds__(128) k_dopri_stage(const AdaptiveArgs<T> A)
         for (int r = 0; r < ConRows<Tp>::NF; ++r) A.con_flags_c[(long long)r * N + c] = A.con_flags[(long long)r * B + lane];
         for (int r = 0; r < ConRows<Tp>::ND; ++r) A.ws[(long long)(R::CDATA + r) * N + c] = A.con_data[(long long)r * B + lane];
     }
+    if (A.stage_time) A.stage_time[lane] = dopri::stage_time((double)A.lane_time[lane], i, A.fs[AD_DT_TRY * B + lane]);
     const T dt = (T)A.fs[AD_DT_TRY * B + lane];
     T q0[NQ], incv[NV], qs[NQ];
     static_for<0, NQ>([&](auto ic) { q0[decltype(ic)::value] = A.q[decltype(ic)::value * B + lane]; });
@@ -338,6 +350,7 @@ __global__ void __launch_bounds__(128) k_dopri_finish(const AdaptiveArgs<T> A)
             A.a[k * B + lane] = ka6[k * N];
         });
         fs[AD_T * B] += dt;
+        if (A.lane_time) A.lane_time[lane] += (T)dt;
         is[AD_SUCC_TOO_LARGE * B] = 0;
         is[AD_SUCC_FAILED * B] = 0;
         is[AD_ITER * B] += 1;

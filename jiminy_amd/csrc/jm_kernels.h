@@ -176,7 +176,10 @@ constexpr int LANE_STRIDE = 64;
 // P[BatchArgs::proc_off ...] (uniform: scalar loads), pointers as the bit pattern of a scalar:
 //   [0] K (1..4) | [1] lane time `[1][B]` (JM_F_LANE_TIME: the lane's time at the start of the integrator step, kept by these kernels)
 //   per component i, at [2 + 6 i]: row | n | h | scale | values | grads
-constexpr int JM_PROC_BLOCK = 2 + 6 * 4;
+//   [26] stage time `[B]`, float64, batch order (null until jm_batch_bind_adaptive): the time of the coming evaluation of every lane
+//   of a stage launch of the per-stage adaptive stepper (k_dopri_stage writes it).  Those launches, and only those, run on a compact
+//   batch (BatchArgs::lane_map): a MODE_DYNAMICS launch with a lane map evaluates at that row, every other launch at lane time.
+constexpr int JM_PROC_BLOCK = 2 + 6 * 4 + 1;
 template<class T> struct ProcBlock
 {
     CPtr<T> p;
@@ -193,6 +196,7 @@ template<class T> struct ProcBlock
     JM_DEV T scale(int i) const { return p[5 + 6 * i]; }
     JM_DEV const T * values(int i) const { return as_ptr<const T>(p[6 + 6 * i]); }
     JM_DEV const T * grads(int i) const { return as_ptr<const T>(p[7 + 6 * i]); }
+    JM_DEV const T * stage_time() const { return as_ptr<const T>(p[26]); }
 };
 template<class T> JM_DEV ProcBlock<T> proc_block(const BatchArgs<T> & A) { return {(CPtr<T>)A.P + A.proc_off}; }
 // Process force `i` at time `t`, for the lane whose column of the tables is `lane` of `stride`: the interpolation of
@@ -1391,6 +1395,7 @@ JM_DEV void lane_run(const BatchArgs<T> & A, long long lane, T * sb,
         if (A.proc_off > 0)
         {
             if (A.mode == MODE_START || A.mode == MODE_RESET) proc_block(A).lane_time()[lane] = T(0);
+            else if (A.lane_map) tl = proc_block(A).stage_time()[A.lane_map[lane]];   // (a stage of the per-stage adaptive stepper)
             else tl = proc_block(A).lane_time()[lane];
         }
         w.t_eval = tl;

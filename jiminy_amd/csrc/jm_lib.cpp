@@ -121,6 +121,7 @@ struct jm_batch
     int32_t * ad_is = nullptr;
     int32_t * ad_count = nullptr;       // device
     int32_t * ad_flags = nullptr;       // device, compact constraint flags [NF][B] (constraint model + adaptive)
+    double * ad_stage_time = nullptr;   // device, [B]: time of the coming stage evaluation of every lane (process forces, per-stage form)
     // compact-batch overrides of the constraint state pointers (adaptive stepper), null = bound fields
     int32_t * ov_flags = nullptr; void * ov_data = nullptr; void * ov_ws = nullptr;
     int32_t * ad_count_host = nullptr;  // pinned host
@@ -156,6 +157,7 @@ int32_t write_process_block(jm_batch * b)
     for (int i = 0; i < jm::JM_PROC_BLOCK; ++i) blk[i] = 0.0;
     blk[0] = (double)b->proc_k;
     blk[1] = bits(b->field[JM_F_LANE_TIME]);
+    blk[26] = bits(b->ad_stage_time);
     for (int i = 0; i < b->proc_k; ++i)
     {
         double * c = blk + 2 + 6 * i;
@@ -481,6 +483,10 @@ template<class T> int32_t step_adaptive(jm_batch * b, double t_next, const jm_ad
     D.t_next = t_next; D.tol_rel = o->tol_rel; D.tol_abs = o->tol_abs; D.dt_max = o->dt_max;
     D.dt_restore_threshold_rel = o->dt_restore_threshold_rel; D.succ_failed_max = o->successive_iter_failed_max;
     D.new_step = new_step; D.stage = 0;
+    // process forces: the per-stage kernels leave the time of every stage for the dynamics launch and advance the lanes' process time
+    const bool proc = b->proc_k > 0 && b->applied_k > 0 && std::is_same<T, double>::value;
+    D.lane_time = proc ? (T *)b->field[JM_F_LANE_TIME] : nullptr;
+    D.stage_time = proc ? b->ad_stage_time : nullptr;
     if (D.status && new_step) HIP_TRY(hipMemsetAsync(D.status, 0, sizeof(int32_t) * B, s));
     // FSAL fix when the command changed at the breakpoint: a(t+) (engine.cc:2030-2042)
     if (command_changed)
@@ -694,6 +700,7 @@ int32_t jm_batch_destroy(jm_batch * b)
     if (b->lane_stat_host) (void)hipHostFree(b->lane_stat_host);
     for (hipEvent_t e : b->lane_ev) if (e) (void)hipEventDestroy(e);
     if (b->ad_flags) (void)hipFree(b->ad_flags);
+    if (b->ad_stage_time) (void)hipFree(b->ad_stage_time);
     if (b->ad_count_host) (void)hipHostFree(b->ad_count_host);
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
     delete b;
@@ -851,6 +858,13 @@ int32_t jm_batch_bind_adaptive(jm_batch * b, void * workspace, double * state_f6
             HIP_TRY(hipMalloc((void **)&b->ad_flags, sizeof(int32_t) * (size_t)jm::ConRows<Topo>::NF * (size_t)b->B));
         HIP_TRY(hipHostMalloc((void **)&b->ad_count_host, 2 * sizeof(int32_t), hipHostMallocDefault));
     }
+    if (!b->ad_stage_time)
+    {
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipMalloc((void **)&b->ad_stage_time, sizeof(double) * (size_t)b->B));
+        HIP_TRY(hipMemset(b->ad_stage_time, 0, sizeof(double) * (size_t)b->B));
+        if (b->proc_k > 0) return write_process_block(b);
+    }
     return JM_OK;
 }
 int32_t jm_batch_step_adaptive(jm_batch * b, double t_next, const jm_adaptive_options * options, int32_t new_step,
@@ -860,8 +874,6 @@ int32_t jm_batch_step_adaptive(jm_batch * b, double t_next, const jm_adaptive_op
     if (!b || !options) return fail(JM_EINVAL, "jm_batch_step_adaptive: null argument");
     if (!b->started)
         return fail(JM_ECONTROLFLOW, "No simulation running. Please start one before using step method.");
-    if (b->proc_k > 0)
-        return fail(JM_ENOTIMPL, "process forces are evaluated by the fixed-step kernels only: the adaptive stepper does not carry the time of its stages");
     if (!b->ad_ws || !b->ad_fs || !b->ad_is)
         return fail(JM_ECONTROLFLOW, "jm_batch_bind_adaptive must be called before the adaptive stepper is used");
     if (b->copt.contact_model == JM_CONTACT_CONSTRAINT && b->dtype != JM_F64)

@@ -99,6 +99,12 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
     int st = D.status ? D.status[r32] : 0;
     int attempts = 0;
     bool moved = false;
+    // process forces (GEN): the robot's process time (JM_F_LANE_TIME, identical in its four lanes); stage i of an attempt is
+    // evaluated at dopri::stage_time(tl, i, dt), accepted steps advance it with `t`, the lead lane stores it
+    double tl = 0.0;
+    (void)tl;
+    if constexpr (GEN)
+        if (A.proc_off > 0) tl = (double)proc_block(A).lane_time()[r32];
     X::sync();
     X::table_ready();
     // limb stage derivatives: rows of the caller's workspace, private to this lane
@@ -192,7 +198,10 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
                     if constexpr (R::LONG) S.putl(R::KVL + s, vl[s]);
                 });
                 int evst = 0;
-                quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, r32, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, evst);
+                T te = T(0);
+                if constexpr (GEN) te = (T)dopri::stage_time(tl, i, dt);
+                quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, r32, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, evst,
+                                                                                nullptr, nullptr, nullptr, te);
                 static_for<0, NVB>([&](auto ic) { S.putb(DR::KAB + (i - 1) * NVB + decltype(ic)::value, ddqb[decltype(ic)::value]); });
                 static_for<0, N>([&](auto sc) { if (ix.has[decltype(sc)::value]) kal[krow(i, decltype(sc)::value)] = ddq[decltype(sc)::value]; });
             }
@@ -314,6 +323,7 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
                 });
                 moved = true;
                 t += dt;
+                if constexpr (GEN) tl += dt;
                 tooLarge = 0; failed = 0; iter += 1;
                 if (bpReached && dt < dtl && dtl < dtLargestPrev * D.dt_restore_threshold_rel) dtl = dtLargestPrev;
                 dtLargestPrev = dtl;
@@ -358,6 +368,8 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
         D.is[AD_SUCC_TOO_LARGE * Bq + r32] = tooLarge; D.is[AD_SUCC_FAILED * Bq + r32] = failed;
         D.is[AD_ACTIVE * Bq + r32] = active ? 1 : 0;
         if (D.status) D.status[r32] = st;
+        if constexpr (GEN)
+            if (A.proc_off > 0) proc_block(A).lane_time()[r32] = (T)tl;
 #ifndef JM_HOST_EMU
         // robots still on their way (attempt bound reached) and the largest attempt count, for the host
         if (active) atomicAdd(D.n_active, 1);

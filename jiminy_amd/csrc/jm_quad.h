@@ -1819,6 +1819,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         if (A.proc_off > 0)
         {
             if (A.mode == MODE_START || A.mode == MODE_RESET) { if (lead) proc_block(A).lane_time()[r32] = T(0); }
+            else if (A.lane_map) tl = proc_block(A).stage_time()[(unsigned)A.lane_map[r32]];   // (a stage of the per-stage adaptive stepper)
             else tl = proc_block(A).lane_time()[r32];
             te = tl;
         }

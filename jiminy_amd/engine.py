@@ -134,8 +134,8 @@ def impulse_active(t_impulse: float, dt_impulse: float, t: float, was_active: bo
     return active
 
 
-_PROCESS_FORCE_ADAPTIVE = ("process forces are evaluated by the fixed-step kernels ('euler_explicit', 'runge_kutta_4'): "
-                           "the adaptive stepper does not carry the time of its stages to them")
+_PROCESS_FORCE_ADAPTIVE = ("with the adaptive stepper a process force is evaluated at the time of every stage of every attempt "
+                           "and takes part in the step-size control: register it with adaptive=True")
 
 
 def launch_pieces(n: int, sensors: bool, per_step_noise: bool, profile_forces: Any, process_forces: Any = ()) -> List[int]:
@@ -591,15 +591,17 @@ def _variation_self_test_leg(model: CompiledModel, variant: int, device: torch.d
     return err
 
 
-_DOPRI_FORM: Dict[Tuple[str, int, bool], int] = {}
+_DOPRI_FORM: Dict[Tuple[str, int, bool, bool], int] = {}
 
 
-def _adaptive_self_test(model: CompiledModel, variant: int, device: torch.device, gen: bool = False) -> float:
+def _adaptive_self_test(model: CompiledModel, variant: int, device: torch.device, gen: bool = False,
+                        process: bool = False) -> float:
     """Persistent adaptive kernel (jm_qdopri.h) against the per-stage launches on the probe batch: three breakpoint
     intervals with tight tolerances.  Returns the largest relative disagreement over (q, v) on the lanes that follow the
     same accept / reject sequence (inf when fewer than 80 % do, or when the persistent kernel flags lanes the per-stage
     path does not).  `gen`: its variation form (`k_quad_dopri_gen`, a separate compilation), selected by a per-lane friction
-    field that holds the nominal coefficient."""
+    field that holds the nominal coefficient.  `process` (the engine that asks has process forces): both probes carry one on
+    the root joint, so that the stage times of the two forms are compared as well."""
     n = 64
     q, v, cmd = (torch.as_tensor(x, dtype=torch.float64, device=device) for x in _probe_state(model, n))
     outs = []
@@ -612,6 +614,15 @@ def _adaptive_self_test(model: CompiledModel, variant: int, device: torch.device
         if gen:
             probe._gen_checked = True      # (the step kernels' own variation check is not what is probed here)
             probe.set_lane_friction(torch.full((n,), float(probe._options["contacts"]["friction"]), dtype=torch.float64))
+        root_frame = next((name for name, f in model.frames.items() if f.parent_joint == 1), None)
+        if process and root_frame is not None:
+            from .processes import PeriodicGaussianProcess
+            # (the same realisation for both forms; over the 3 ms of the probe the force changes by some 1e-2 of its scale,
+            # 20 m/s^2 on the whole robot: a stage evaluated at another time shows far above the 1e-6 of the comparison)
+            proc = PeriodicGaussianProcess(0.2, 1.0, n, device=device)
+            proc.reset(torch.Generator().manual_seed(5))
+            probe._gen_checked = True
+            probe.register_process_force(root_frame, proc, 0, scale=20.0 * float(np.sum(model.mass)), adaptive=True)
         if model.nmotors:
             probe.set_command(cmd)
         probe.start(q, v)
@@ -1405,8 +1416,6 @@ class BatchedEngine:
         for pf in self._profile_forces:
             pf["value"], pf["t_last"] = None, -math.inf
         self._impulse_active = []
-        if self._process_forces and self._options["stepper"]["odeSolver"] == "runge_kutta_dopri":
-            raise NotImplementedError(_PROCESS_FORCE_ADAPTIVE)
         self._update_applied_forces(0.0)
         self._check_variation_kernels()
         self._lib.check(self._L.jm_batch_start(self._batch_h, self._stream()))
@@ -1457,8 +1466,9 @@ class BatchedEngine:
 
     def _step_adaptive(self, step_dt: float) -> None:
         st = self._options["stepper"]
-        # (impulse / profile forces and per-lane model biases: available where the stepper is the persistent kernel
-        # of jm_qdopri.h, whose lanes keep their places; the per-stage path over compacted lanes refuses them)
+        # (impulse / profile forces, process forces and per-lane model biases: the persistent kernel of jm_qdopri.h keeps
+        # every lane in its place; the per-stage path over compacted lanes reads those rows through the launch's lane map.
+        # Process forces are evaluated by both at the time of every stage: neither a breakpoint nor a forced a(t+) refresh)
         intervals, t_end, t_err = plan_breakpoints(self._t, self._t_error, float(step_dt), self._options,
                                                    self._force_breakpoints(self._t))
         o = _abi.AdaptiveOptions(float(st["tolRel"]), float(st["tolAbs"]), float(st["dtMax"]),
@@ -1507,10 +1517,11 @@ class BatchedEngine:
         # (the variation form of the kernel -- per-lane body parameters / friction, height map, applied forces: jm_lib.cpp
         # `step_adaptive` -- is a compilation of its own and is checked on its own)
         gen = self._variation_kernels_in_use("friction" in self._fields)
-        key = (self.model.topology_hash(), self._lib_variant_index, gen)
+        process = bool(self._process_forces)
+        key = (self.model.topology_hash(), self._lib_variant_index, gen, process)
         if key not in _DOPRI_FORM:
             _DOPRI_FORM[key] = 0       # (the probes below are engines of the same topology)
-            err = _adaptive_self_test(self.model, self._lib_variant_index, self.device, gen=gen)
+            err = _adaptive_self_test(self.model, self._lib_variant_index, self.device, gen=gen, process=process)
             if not err <= 1e-6:
                 _DOPRI_FORM[key] = 1
                 warnings.warn(f"{self.model.name}: the persistent adaptive kernel{' (variation form)' if gen else ''} of build variant "
@@ -1856,7 +1867,8 @@ class BatchedEngine:
         self._profile_forces.append({"frame": self._force_frame_index(frame_name), "func": func,
                                      "period": float(update_period), "t_last": -math.inf, "value": None})
 
-    def register_process_force(self, frame_name: str, process: Any, component: int, scale: float = 1.0) -> None:
+    def register_process_force(self, frame_name: str, process: Any, component: int, scale: float = 1.0,
+                               adaptive: bool = False) -> None:
         """A continuous profile force the DEVICE evaluates: component `component` (0..2 force x y z, 3..5 moment, world
         aligned) of the wrench on `frame_name` is `scale * process(lane time)`, added to the held impulse / profile value
         of that frame.  `process` is a `PeriodicGaussianProcess` (or Fourier) of this batch size on this device; its
@@ -1864,10 +1876,13 @@ class BatchedEngine:
         evaluation -- what `Engine::computeExternalForces` does with a profile force of update period 0
         (engine.cc:3482-3494) -- so `process.reset(...)` between launches takes effect without a new registration.
         Lane time (`lane_time`) is 0 at `start` and for the lanes of `reset_lanes`, and advances with every integrator
-        step.  Such forces neither cut launches nor force an a(t+) refresh.  At most 4 components; fixed-step solvers."""
+        step (an accepted one, under the adaptive solver, whose stage i is evaluated at lane time + c_i dt).  Such forces neither
+        cut launches nor force an a(t+) refresh.  At most 4 components; float64 batches.  While the solver is
+        `runge_kutta_dopri` a registration has to say `adaptive=True` (a plain call is refused, as it always was): the force
+        then enters the error estimate of every attempt and so the step sizes the lanes choose."""
         if self._running:
             raise BadControlFlow("Simulation already running. Please stop it before registering new forces.")
-        if self._options["stepper"]["odeSolver"] == "runge_kutta_dopri":
+        if self._options["stepper"]["odeSolver"] == "runge_kutta_dopri" and not adaptive:
             raise NotImplementedError(_PROCESS_FORCE_ADAPTIVE)
         if len(self._process_forces) >= 4:
             raise ValueError("at most 4 process force components can be registered")

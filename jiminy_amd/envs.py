@@ -367,7 +367,8 @@ class VecJiminyEnv:
         if self._disturbance_on_device:
             # lane time (0 at `start` and for the lanes of `reset_lanes`) is the episode time of every environment
             for component, proc in enumerate(self._f_xy_profile):
-                self.engine.register_process_force(frame, proc, component, self.F_PROFILE_SCALE * scale)
+                # (`adaptive=True`: under `runge_kutta_dopri` the kernels evaluate it at the time of every stage)
+                self.engine.register_process_force(frame, proc, component, self.F_PROFILE_SCALE * scale, adaptive=True)
             return
 
         def profile(t: float, q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:

@@ -3,7 +3,10 @@
     python tools/bench_process_force.py [--envs 65536 4096] [--steps 200] [--warmup 10] [--repeats 3] [--root CHECKOUT]
 One environment step (`make_anymal_env`, PD pipeline) in every combination of
   * B = `--envs`;
-  * explicit Euler with the shipped periods (dtMax 1e-3, controller 5 ms), and RK4 at dtMax 1e-3;
+  * explicit Euler with the shipped periods (dtMax 1e-3, controller 5 ms), and RK4 at dtMax 1e-3; `--solvers` also takes
+    `runge_kutta_dopri` (the adaptive stepper, `--dopri-dt-max`, tolerances of the reference's defaults): its `callable` leg
+    holds the force over a whole controller period, its `process` leg evaluates it at the time of every stage, it has no
+    `process_graph` leg (the adaptive loop synchronises with the host), and every row names the form of the stepper that served it;
   * spring-damper and constraint contact model;
   * legs: `undisturbed`; `callable` = std_ratio['disturbance'] through the host callable (re-evaluated at the start of every
     integrator step, launches cut to one step, an a(t+) refresh per launch); `process` = the same disturbance with the two
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--legs", nargs="+", default=["undisturbed", "callable", "process", "process_graph"])
     ap.add_argument("--solvers", nargs="+", default=["euler_explicit", "runge_kutta_4"])
     ap.add_argument("--contact-models", nargs="+", default=["spring_damper", "constraint"])
+    ap.add_argument("--dopri-dt-max", type=float, default=1e-3)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
@@ -51,17 +55,20 @@ def main():
         for solver in args.solvers:
             for contact_model in args.contact_models:
                 envs = {}
-                for leg in legs:
-                    env = make_anymal_env(B, device=dev, ode_solver=solver, dt_max=1e-3, contact_model=contact_model, **leg_kw[leg])
+                adaptive = solver == "runge_kutta_dopri"
+                dt_max = args.dopri_dt_max if adaptive else 1e-3
+                legs_here = [leg for leg in legs if not (adaptive and leg == "process_graph")]
+                for leg in legs_here:
+                    env = make_anymal_env(B, device=dev, ode_solver=solver, dt_max=dt_max, contact_model=contact_model, **leg_kw[leg])
                     if leg == "process_graph":
                         env.enable_graph()
                     env.reset(seed=0)
                     for _ in range(args.warmup):
                         env.step(action)
                     envs[leg] = env
-                times = {leg: [] for leg in legs}
+                times = {leg: [] for leg in legs_here}
                 for _ in range(args.repeats):
-                    for leg in legs:          # alternating legs: drift of the machine hits all of them alike
+                    for leg in legs_here:     # alternating legs: drift of the machine hits all of them alike
                         env = envs[leg]
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
@@ -70,9 +77,14 @@ def main():
                         torch.cuda.synchronize()
                         times[leg].append(1e3 * (time.perf_counter() - t0) / args.steps)
                 row = {"envs": B, "solver": solver, "contact_model": contact_model}
-                for leg in legs:
+                if adaptive:
+                    row["dt_max"] = dt_max
+                for leg in legs_here:
                     row[leg] = {"median_ms": round(statistics.median(times[leg]), 4),
                                 "spread_ms": round(max(times[leg]) - min(times[leg]), 4)}
+                    if adaptive:      # (0: the persistent kernel where the library has one for this batch, 1: per-stage launches)
+                        forced = envs[leg].engine._adaptive_form() == 1 or contact_model != "spring_damper"
+                        row[leg]["form"] = "per-stage" if forced else "persistent"
                 out["results"].append(row)
                 print(json.dumps(row), file=sys.stderr, flush=True)
                 del envs
