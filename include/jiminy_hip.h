@@ -566,6 +566,56 @@ int32_t jm_block_deformation_estimator(const jm_deform_plan * plan, int32_t dtyp
                                        const void * encoder, const void * imu_quat, void * out_quat, void * out_rpy,
                                        void * stream);
 
+/* ---- Attitude observers: the `MahonyFilter` block around its filter function, and the `BodyObserver` block; batched, one
+ * lane = one environment.  New symbols only: no existing structure or signature changed with them.
+ * jm_attitude_desc: the plan (host arrays, copied by jm_attitude_plan_create).  Per IMU sensor (sensor order): the filter
+ *   gains `kp`, `ki`, the rotation of the sensor frame relative to its parent body as a quaternion `rel_quat` (xyzw,
+ *   `matrices_to_quat` rule) and the world rotation of the sensor frame as a list of segments
+ *   `frame_seg_start[s] .. frame_seg_start[s + 1] - 1`: a segment is a constant rotation `seg_rot` (row-major 3x3) followed by a
+ *   joint rotation read from the configuration rows `q` `[nq][B]` at `seg_q_index`: `seg_kind` 0 none, 1 / 2 / 3 about x / y / z
+ *   by the angle `q[i]`, 4 about the unit vector `seg_axis` by `q[i]`, 5 about `seg_axis` with `(cos, sin) = q[i], q[i + 1]`
+ *   (unbounded revolute joint), 6 the unit quaternion `q[i .. i + 3]` (xyzw: spherical joint, free-flyer orientation).
+ *   Prismatic joints contribute nothing.  jm_attitude_plan_create validates the description (JM_EINVAL + jm_last_error,
+ *   before any device call) and uploads it; the three calls then allocate, copy and synchronise nothing.
+ * jm_block_attitude_init ≙ `MahonyFilter.refresh_observation` while the filter is not initialised
+ *   (python/gym_jiminy/common/gym_jiminy/common/blocks/mahony_filter.py:340-374), on the lanes of `lane_mask` (device, uint8
+ *   `[B]`; NULL: every lane; other lanes are not touched): `exact_init` the true orientation of the sensor frames from `q`,
+ *   else `swing_from_vector` of the normalised accelerometer rows of `imu` (raw JM_F_IMU field `[n_imu][6][B]`), falling back
+ *   to the true orientation on lanes where every accelerometer component is below 0.1 g.  Writes `quat` `[4][n_imu][B]`
+ *   (xyzw), zeroes `omega`, `cf`, `bias` `[3][n_imu][B]` and `twist` `[n_imu][B]` (or NULL), writes `rpy` `[3][n_imu][B]` (or NULL).
+ * jm_block_mahony_observer ≙ one later refresh (:376-393): `mahony_filter` with the gains of every IMU, then
+ *   `remove_twist_from_quat` (`ignore_twist`) and `quat_to_rpy` (`rpy` not NULL) -- also after the filter's early return.
+ * jm_block_body_observer ≙ `BodyObserver.refresh_observation` (blocks/body_orientation_observer.py:237-266):
+ *   `quat = imu_quat * conj(rel_quat)`, `omega = rel_quat applied to imu_omega`, then by `twist_mode` 0 nothing, 1
+ *   `remove_twist_from_quat`, 2 that and `update_twist` (:26-71) with the leak `max(0, 1 - time_constant_inv * dt)` on the
+ *   state `twist` `[n_imu][B]` (NULL allowed for modes 0, 1); `rpy` or NULL.  `quat` must not alias `imu_quat`. */
+typedef struct jm_attitude_desc
+{
+    int32_t n_imu;
+    int32_t nq;                         /* rows of q: the range of seg_q_index */
+    const double * kp;                  /* [n_imu] */
+    const double * ki;                  /* [n_imu] */
+    const double * rel_quat;            /* [n_imu][4] */
+    const int32_t * frame_seg_start;    /* [n_imu + 1], ascending, last = n_seg */
+    int32_t n_seg;
+    const int32_t * seg_kind;           /* [n_seg] */
+    const int32_t * seg_q_index;        /* [n_seg], -1 where seg_kind is 0 */
+    const double * seg_rot;             /* [n_seg][9] */
+    const double * seg_axis;            /* [n_seg][3] */
+} jm_attitude_desc;
+typedef struct jm_attitude_plan jm_attitude_plan;
+int32_t jm_attitude_plan_create(const jm_attitude_desc * desc, jm_attitude_plan ** out);
+int32_t jm_attitude_plan_destroy(jm_attitude_plan * plan);
+int32_t jm_block_attitude_init(const jm_attitude_plan * plan, int32_t dtype, int64_t batch_size, const void * q,
+                               const void * imu, const uint8_t * lane_mask, int32_t exact_init, void * quat, void * omega,
+                               void * cf, void * bias, void * twist, void * rpy, void * stream);
+int32_t jm_block_mahony_observer(const jm_attitude_plan * plan, int32_t dtype, int64_t batch_size, const void * imu,
+                                 void * quat, void * omega, void * cf, void * bias, double dt, int32_t ignore_twist,
+                                 void * rpy, void * stream);
+int32_t jm_block_body_observer(const jm_attitude_plan * plan, int32_t dtype, int64_t batch_size, const void * imu_quat,
+                               const void * imu_omega, void * quat, void * omega, void * twist, int32_t twist_mode,
+                               double time_constant_inv, double dt, void * rpy, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

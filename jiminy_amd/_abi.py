@@ -88,6 +88,17 @@ class DeformDesc(C.Structure):
     ]
 
 
+class AttitudeDesc(C.Structure):
+    """jm_attitude_desc: the plan of the attitude observers (jiminy_amd.attitude builds it)."""
+    _fields_ = [
+        ("n_imu", C.c_int32), ("nq", C.c_int32),
+        ("kp", _pd), ("ki", _pd), ("rel_quat", _pd),
+        ("frame_seg_start", _pi),
+        ("n_seg", C.c_int32), ("seg_kind", _pi), ("seg_q_index", _pi),
+        ("seg_rot", _pd), ("seg_axis", _pd),
+    ]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

@@ -51,6 +51,8 @@ ABI_SYMBOLS = (
     "jm_block_model_bias", "jm_engine_rng_seed",
     "jm_deform_plan_create", "jm_deform_plan_destroy", "jm_block_deformation_estimator",
     "jm_batch_set_process_forces",
+    "jm_attitude_plan_create", "jm_attitude_plan_destroy", "jm_block_attitude_init", "jm_block_mahony_observer",
+    "jm_block_body_observer",
 )
 
 
@@ -106,6 +108,12 @@ class HipLibrary:
         L.jm_deform_plan_create.argtypes = [C.POINTER(_abi.DeformDesc), C.POINTER(vp)]
         L.jm_deform_plan_destroy.argtypes = [vp]
         L.jm_block_deformation_estimator.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp]
+        L.jm_attitude_plan_create.argtypes = [C.POINTER(_abi.AttitudeDesc), C.POINTER(vp)]
+        L.jm_attitude_plan_destroy.argtypes = [vp]
+        L.jm_block_attitude_init.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+        L.jm_block_mahony_observer.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_double, C.c_int32, vp, vp]
+        L.jm_block_body_observer.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_double,
+                                             vp, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

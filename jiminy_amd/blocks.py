@@ -18,6 +18,11 @@ launches; `pd_adapter` below is the tensor-program form.
 `DeformationEstimator` is the observer block of that name (blocks/deformation_estimator.py): one HIP launch
 (csrc/jm_deform.h behind `jm_block_deformation_estimator`) driven by a plan that jiminy_amd/deformation.py builds on the host.
 It has no tensor-program form: its specification is the reference's own output (tests/golden/ref_deformation.npz).
+
+`MahonyFilter` and `BodyObserver` are the observer blocks of those names with every option of the reference's classes
+(blocks/mahony_filter.py:104-393, blocks/body_orientation_observer.py:74-266): per-IMU gains, twist removal, Euler angles, the
+initialisation at the first refresh of an episode, the body frames and the leaky twist integrator.  One HIP launch per
+refresh (csrc/jm_attitude.h) driven by a plan that jiminy_amd/attitude.py builds; specification: tests/golden/ref_attitude.npz.
 """
 from __future__ import annotations
 
@@ -188,6 +193,164 @@ class DeformationEstimator:
                 self._L.jm_deform_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
+
+
+def _check_block_tensor(eng, t: torch.Tensor) -> None:
+    if not t.is_contiguous() or t.device != eng.device or t.dtype != eng.dtype:
+        raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+
+
+class MahonyFilter:
+    """≙ `gym_jiminy.common.blocks.MahonyFilter` (blocks/mahony_filter.py:104-393), batched over the IMU sensors of the
+    engine's model (sensor order) and its lanes.
+
+    Observation: `quat` `[4][n_imu][B]` (xyzw), `omega` `[3][n_imu][B]`, `rpy` `[3][n_imu][B]` (`compute_rpy`, else None);
+    state: `bias` `[3][n_imu][B]`.  `reset(lane_mask)` is the first refresh of an episode (:340-374: the true orientation
+    of the IMU frames with `exact_init`, else from the accelerometers) and reads the engine's `q` and IMU rows: call it
+    after the engine's `start` / `reset_lanes`.  `refresh(dt)` is every later one (:376-393).  One launch each."""
+
+    def __init__(self, engine, *, ignore_twist: bool = False, exact_init: bool = True, kp=1.0, ki=0.1,
+                 compute_rpy: bool = False) -> None:
+        import ctypes as C
+
+        from . import _abi, attitude
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.plan = attitude.build_plan(engine.model, kp, ki)
+        self.ignore_twist, self.exact_init, self.compute_rpy = bool(ignore_twist), bool(exact_init), bool(compute_rpy)
+        self.kp, self.ki = self.plan.kp, self.plan.ki
+        n_imu, B = self.plan.n_imu, engine.batch_size
+        new = lambda rows: torch.zeros((rows, n_imu, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
+        self.quat, self.omega, self.bias, self._cf = new(4), new(3), new(3), new(3)
+        self.quat[3] = 1.0      # (:286)
+        self.rpy = new(3) if compute_rpy else None
+        self._twist_of = None   # the `twist` state of a BodyObserver behind this filter: zeroed by the same launch
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_attitude_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        """≙ `MahonyFilter.fieldnames` (:321-335)."""
+        imu = self.plan.imu_names
+        names = {"quat": [[f"{n}.Quat{e}" for n in imu] for e in ("X", "Y", "Z", "W")],
+                 "omega": [[f"{n}.{e}" for n in imu] for e in ("X", "Y", "Z")]}
+        if self.compute_rpy:
+            names["rpy"] = [[f"{n}.{e}" for n in imu] for e in ("Roll", "Pitch", "Yaw")]
+        return names
+
+    def _vp(self, t: Optional[torch.Tensor]):
+        if t is None:
+            return None
+        _check_block_tensor(self._eng, t)
+        return self._C.c_void_p(t.data_ptr())
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        eng = self._eng
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        twist = None if self._twist_of is None else self._twist_of.twist
+        self._check(self._L.jm_block_attitude_init(
+            self._plan, self._dtype, eng.batch_size, self._vp(eng.field("q")), self._vp(eng.field("imu")),
+            None if mask is None else self._C.c_void_p(mask.data_ptr()), int(self.exact_init), self._vp(self.quat),
+            self._vp(self.omega), self._vp(self._cf), self._vp(self.bias), self._vp(twist), self._vp(self.rpy), eng._stream()))
+
+    def refresh(self, dt: float) -> None:
+        eng = self._eng
+        if not dt > 0.0:
+            raise ValueError("This block does not support time-continuous update.")     # (:288-291)
+        self._check(self._L.jm_block_mahony_observer(
+            self._plan, self._dtype, eng.batch_size, self._vp(eng.field("imu")), self._vp(self.quat), self._vp(self.omega),
+            self._vp(self._cf), self._vp(self.bias), float(dt), int(self.ignore_twist), self._vp(self.rpy), eng._stream()))
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_attitude_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+class BodyObserver:
+    """≙ `gym_jiminy.common.blocks.BodyObserver` (blocks/body_orientation_observer.py:74-266) behind a `MahonyFilter`:
+    orientation `quat` `[4][n_imu][B]`, angular velocity `omega` `[3][n_imu][B]` and `rpy` (`compute_rpy`, else None) of
+    the parent body of every IMU.  `twist_time_constant`: None keeps the filter's twist, 0 removes it, > 0 removes it and
+    estimates it with a leaky integrator (state `twist` `[n_imu][B]`)."""
+
+    def __init__(self, engine, mahony: MahonyFilter, *, twist_time_constant: Optional[float] = None,
+                 compute_rpy: bool = True) -> None:
+        from . import attitude
+        if mahony._eng is not engine:
+            raise ValueError("the Mahony filter belongs to another engine")
+        self._eng, self._mahony = engine, mahony
+        self.compute_rpy = bool(compute_rpy)
+        # (:129-140)
+        if twist_time_constant is None:
+            self.twist_time_constant_inv, self._mode = None, attitude.TWIST_KEEP
+        elif twist_time_constant > 0.0:
+            self.twist_time_constant_inv, self._mode = 1.0 / float(twist_time_constant), attitude.TWIST_INTEGRATE
+        else:
+            self.twist_time_constant_inv, self._mode = float("inf"), attitude.TWIST_REMOVE
+        n_imu, B = mahony.plan.n_imu, engine.batch_size
+        new = lambda rows: torch.zeros((rows, n_imu, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
+        self.quat, self.omega = new(4), new(3)
+        self.quat[3] = 1.0      # (:219)
+        self.rpy = new(3) if compute_rpy else None
+        self.twist = torch.zeros((n_imu, B), dtype=engine.dtype, device=engine.device)
+        mahony._twist_of = self
+        self._scratch = None
+
+    @property
+    def fieldnames(self):
+        """≙ `BodyObserver.fieldnames` (:221-235)."""
+        imu = self._mahony.plan.imu_names
+        names = {"quat": [[f"{n}.Quat{e}" for n in imu] for e in ("X", "Y", "Z", "W")]}
+        if self.compute_rpy:
+            names["rpy"] = [[f"{n}.{e}" for n in imu] for e in ("Roll", "Pitch", "Yaw")]
+        names["omega"] = [[f"{n}.{e}" for n in imu] for e in ("X", "Y", "Z")]
+        return names
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The first refresh of an episode on the masked lanes: the reference refreshes every observer once at reset,
+        behind the filter's initialisation, with a zero twist estimate and a zero angular velocity (:211-219, :237-266) --
+        the twist, if any, is removed and nothing is integrated.  Call it after the filter's `reset`, which zeroes the twist
+        state of those lanes.  The other lanes keep their observation bit for bit (selection, not arithmetic)."""
+        if lane_mask is None:
+            self._launch(0.0, False, self.quat, self.omega, self.rpy)
+            return
+        mask = lane_mask.to(device=self._eng.device, dtype=torch.bool)      # (any mask dtype, as `MahonyFilter.reset` takes)
+        if tuple(mask.shape) != (self._eng.batch_size,):
+            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
+        if self._scratch is None:
+            self._scratch = (torch.empty_like(self.quat), torch.empty_like(self.omega),
+                             None if self.rpy is None else torch.empty_like(self.rpy))
+        self._launch(0.0, False, *self._scratch)
+        m = mask[None, None, :]
+        for mine, fresh in zip((self.quat, self.omega, self.rpy), self._scratch):
+            if mine is not None:
+                mine.copy_(torch.where(m, fresh, mine))
+
+    def refresh(self, dt: float) -> None:
+        """≙ `refresh_observation` (:237-266): one launch on the engine's stream."""
+        self._launch(dt, True, self.quat, self.omega, self.rpy)
+
+    def _launch(self, dt: float, integrate: bool, quat, omega, rpy) -> None:
+        from . import attitude
+        eng, m = self._eng, self._mahony
+        mode = self._mode if integrate or self._mode != attitude.TWIST_INTEGRATE else attitude.TWIST_REMOVE
+        tci = self.twist_time_constant_inv if mode == attitude.TWIST_INTEGRATE else 0.0
+        m._check(m._L.jm_block_body_observer(
+            m._plan, m._dtype, eng.batch_size, m._vp(m.quat), m._vp(m.omega), m._vp(quat), m._vp(omega),
+            m._vp(self.twist), int(mode), float(tci), float(dt), m._vp(rpy), eng._stream()))
 
 
 def integrate_zoh(state: torch.Tensor, state_min: torch.Tensor, state_max: torch.Tensor,

@@ -28,6 +28,7 @@
 #include "jm_pack.h"
 #include "jm_blocks.h"
 #include "jm_deform.h"
+#include "jm_attitude.h"
 #include "jm_adaptive.h"
 #include "jm_qdopri.h"
 #include "jm_random.h"
@@ -1103,6 +1104,113 @@ int32_t jm_block_deformation_estimator(const jm_deform_plan * p, int32_t dtype, 
     else
         hipLaunchKernelGGL((jm::k_deformation_estimator<float>), dim3(grid), dim3(256), 0, s, a, (const float *)encoder,
                            (const float *)imu_quat, (float *)out_quat, (float *)out_rpy, (long long)B);
+    HIP_TRY(hipGetLastError());
+    return JM_OK;
+}
+
+// ---- attitude observers (MahonyFilter options, BodyObserver): one plan, three single-launch calls
+struct jm_attitude_plan
+{
+    int32_t * d_it = nullptr;
+    double * d_dt = nullptr;
+    int n_imu = 0;
+};
+
+int32_t jm_attitude_plan_create(const jm_attitude_desc * desc, jm_attitude_plan ** out)
+{
+    if (!out) return fail(JM_EINVAL, "jm_attitude_plan_create: null argument");
+    *out = nullptr;
+    std::vector<int32_t> it;
+    std::vector<double> dt;
+    std::string why;
+    if (!jm::attitude_pack(desc, it, dt, why)) return fail(JM_EINVAL, why);
+    jm_attitude_plan * p = new (std::nothrow) jm_attitude_plan;
+    if (!p) return fail(JM_ERUNTIME, "out of host memory");
+    p->n_imu = desc->n_imu;
+    hipError_t e = hipMalloc((void **)&p->d_it, it.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_dt, dt.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(p->d_it, it.data(), it.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_dt, dt.data(), dt.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)jm_attitude_plan_destroy(p);
+        return fail(JM_ERUNTIME, std::string("jm_attitude_plan_create: ") + hipGetErrorString(e));
+    }
+    *out = p;
+    return JM_OK;
+}
+
+int32_t jm_attitude_plan_destroy(jm_attitude_plan * p)
+{
+    if (!p) return JM_OK;
+    if (p->d_it) (void)hipFree(p->d_it);
+    if (p->d_dt) (void)hipFree(p->d_dt);
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_attitude_init(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * q, const void * imu,
+                               const uint8_t * lane_mask, int32_t exact_init, void * quat, void * omega, void * cf, void * bias,
+                               void * twist, void * rpy, void * stream)
+{
+    if (!p || !q || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_attitude_init: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_attitude_init: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_attitude_init: bad dtype");
+    const jm::AttitudeArgs a{p->d_it, p->d_dt, p->n_imu};
+    const unsigned grid = (unsigned)((B + 255) / 256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (dtype == JM_F64)
+        hipLaunchKernelGGL((jm::k_attitude_init<double>), dim3(grid), dim3(256), 0, s, a, (int)(exact_init != 0), (const double *)q,
+                           (const double *)imu, lane_mask, (double *)quat, (double *)omega, (double *)cf, (double *)bias,
+                           (double *)twist, (double *)rpy, (long long)B);
+    else
+        hipLaunchKernelGGL((jm::k_attitude_init<float>), dim3(grid), dim3(256), 0, s, a, (int)(exact_init != 0), (const float *)q,
+                           (const float *)imu, lane_mask, (float *)quat, (float *)omega, (float *)cf, (float *)bias,
+                           (float *)twist, (float *)rpy, (long long)B);
+    HIP_TRY(hipGetLastError());
+    return JM_OK;
+}
+
+int32_t jm_block_mahony_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu, void * quat, void * omega,
+                                 void * cf, void * bias, double dt, int32_t ignore_twist, void * rpy, void * stream)
+{
+    if (!p || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_observer: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_mahony_observer: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_observer: bad dtype");
+    const jm::AttitudeArgs a{p->d_it, p->d_dt, p->n_imu};
+    const unsigned grid = (unsigned)((B + 255) / 256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (dtype == JM_F64)
+        hipLaunchKernelGGL((jm::k_mahony_observer<double>), dim3(grid), dim3(256), 0, s, a, (const double *)imu, (double *)quat,
+                           (double *)omega, (double *)cf, (double *)bias, dt, (int)(ignore_twist != 0), (double *)rpy, (long long)B);
+    else
+        hipLaunchKernelGGL((jm::k_mahony_observer<float>), dim3(grid), dim3(256), 0, s, a, (const float *)imu, (float *)quat,
+                           (float *)omega, (float *)cf, (float *)bias, dt, (int)(ignore_twist != 0), (float *)rpy, (long long)B);
+    HIP_TRY(hipGetLastError());
+    return JM_OK;
+}
+
+int32_t jm_block_body_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu_quat, const void * imu_omega,
+                               void * quat, void * omega, void * twist, int32_t twist_mode, double time_constant_inv, double dt,
+                               void * rpy, void * stream)
+{
+    if (!p || !imu_quat || !imu_omega || !quat || !omega) return fail(JM_EINVAL, "jm_block_body_observer: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_body_observer: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_body_observer: bad dtype");
+    if (twist_mode < 0 || twist_mode > 2) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode must be 0, 1 or 2");
+    if (twist_mode == 2 && !twist) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode 2 needs the twist state");
+    if (quat == imu_quat) return fail(JM_EINVAL, "jm_block_body_observer: quat must not alias imu_quat");
+    const jm::AttitudeArgs a{p->d_it, p->d_dt, p->n_imu};
+    const unsigned grid = (unsigned)((B + 255) / 256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (dtype == JM_F64)
+        hipLaunchKernelGGL((jm::k_body_observer<double>), dim3(grid), dim3(256), 0, s, a, (const double *)imu_quat,
+                           (const double *)imu_omega, (double *)quat, (double *)omega, (double *)twist, (int)twist_mode,
+                           time_constant_inv, dt, (double *)rpy, (long long)B);
+    else
+        hipLaunchKernelGGL((jm::k_body_observer<float>), dim3(grid), dim3(256), 0, s, a, (const float *)imu_quat,
+                           (const float *)imu_omega, (float *)quat, (float *)omega, (float *)twist, (int)twist_mode,
+                           time_constant_inv, dt, (float *)rpy, (long long)B);
     HIP_TRY(hipGetLastError());
     return JM_OK;
 }

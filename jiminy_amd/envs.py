@@ -506,7 +506,9 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                  joint_position_margin: float = 0.0, joint_velocity_limit: float = float("inf"),
                  joint_acceleration_limit: Optional[float] = None,
                  safety_limit: Optional[Dict[str, float]] = None,
-                 deformation_estimator: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
+                 deformation_estimator: Optional[Dict[str, Any]] = None,
+                 mahony_filter: Optional[Dict[str, Any]] = None, body_observer: Optional[Dict[str, Any]] = None,
+                 **kw: Any) -> None:
         opts = kw.pop("engine_options", None) or {}
         st = dict(opts.get("stepper", {}))
         st.setdefault("controllerUpdatePeriod", control_dt)
@@ -576,6 +578,35 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                 hi=np.array([model.position_upper[m.idx_q] * m.reduction for m in model.motors]) - red * margin,
                 vlim=np.minimum(np.array([m.velocity_limit for m in model.motors]), red * vmax))
 
+        # optional full `MahonyFilter` block (gym_jiminy blocks/mahony_filter.py:104-393) in place of the bare filter function:
+        # `dict(ignore_twist=False, exact_init=True, kp=mahony_kp, ki=mahony_ki, compute_rpy=False, update_ratio=1 | -1)`, and
+        # behind it the optional `BodyObserver` (blocks/body_orientation_observer.py): `dict(twist_time_constant=None,
+        # compute_rpy=True, update_ratio=1 | -1)`.  Their state replaces `imu_quat` / `_bias` / `_omega` / `_cf`, so that
+        # whatever reads the attitude estimates (the deformation estimator, `_pipeline_sum`) reads the same tensors as before.
+        self._mahony = self._body = None
+        if body_observer is not None and mahony_filter is None:
+            raise ValueError("body_observer reads the estimates of the MahonyFilter block: give mahony_filter as well")
+        if mahony_filter is not None:
+            if self._hip_blocks is None:
+                raise NotImplementedError("the MahonyFilter / BodyObserver blocks run as HIP blocks")
+
+            def block_config(name: str, given: Dict[str, Any]) -> Tuple[Dict[str, Any], bool]:
+                cfg = dict(given)
+                ratio = int(cfg.pop("update_ratio", 1))
+                if ratio not in (1, -1):
+                    raise NotImplementedError(f"{name}: update_ratio must be 1 (every controller tick) or -1 "
+                                              "(every environment step)")
+                return cfg, ratio == 1
+            cfg, self._mahony_every_tick = block_config("mahony_filter", mahony_filter)
+            cfg.setdefault("kp", self.mahony_kp)
+            cfg.setdefault("ki", self.mahony_ki)
+            self._mahony = blocks.MahonyFilter(self.engine, **cfg)
+            self.imu_quat, self._bias = self._mahony.quat, self._mahony.bias
+            self._omega, self._cf = self._mahony.omega, self._mahony._cf
+            if body_observer is not None:
+                cfg, self._body_every_tick = block_config("body_observer", body_observer)
+                self._body = blocks.BodyObserver(self.engine, self._mahony, **cfg)
+
         # optional `DeformationEstimator` observer behind the Mahony filter (gym_jiminy blocks/deformation_estimator.py):
         # `dict(imu_frame_names=..., flex_frame_names=..., ignore_twist=True, compute_rpy=True, update_ratio=1 | -1)`; it reads
         # `imu_quat` after the filter of every controller tick (`update_ratio` 1) or once per environment step (-1)
@@ -627,6 +658,27 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
         if self._deform is not None:
             self._deform.reset(lane_mask)
 
+    def _init_observers(self, lane_mask: Optional[torch.Tensor]) -> None:
+        """The first refresh of an episode (mahony_filter.py:340-374), from the state and the IMU rows the engine's `start` /
+        `reset_lanes` just wrote."""
+        if self._mahony is not None:
+            self._mahony.reset(lane_mask)
+            if self._body is not None:
+                self._body.reset(lane_mask)
+
+    # (not in `_on_reset`: that hook runs before the engine's `start` / `reset_lanes`, and the initialisation reads the `q`
+    # and IMU rows they write.  The auto-reset of `step` goes through `self.reset_lanes`, so it is covered as well.)
+    def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
+        out = super().reset(seed, options)
+        if self._mahony is None:
+            return out
+        self._init_observers(None)
+        return self.observation(), out[1]
+
+    def reset_lanes(self, lane_mask: torch.Tensor) -> None:
+        super().reset_lanes(lane_mask)
+        self._init_observers(lane_mask)
+
     # ------------------------------------------------------------------ HIP-graph replay of one environment step
     def enable_graph(self, enable: bool = True, whole_step: bool = False) -> None:
         """Replay the launches of one environment step -- PD adapter, then per controller tick PD controller -> physics
@@ -654,6 +706,9 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
             if whole_step and (not self.auto_reset or float(self.std_ratio.get("ground", 0.0)) > 0.0 or
                                self._ground_patch_extent is not None):
                 raise NotImplementedError("whole-step graphs need auto_reset and no ground-friction / terrain-patch randomisation")
+            if whole_step and self._mahony is not None:
+                raise NotImplementedError("whole-step graphs do not take the MahonyFilter / BodyObserver blocks: their "
+                                          "initialisation at reset is not part of the captured step")
             if whole_step and (eng._process_forces or float(self.std_ratio.get("disturbance", 0.0)) > 0.0):
                 raise NotImplementedError("whole-step graphs take no disturbance: their reset draws new realisations")
         self._graph_enabled = bool(enable)
@@ -766,7 +821,14 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                                      self.control_dt, self._torque)
                 self.engine.set_command(self._torque)
             self.engine.step(self.control_dt)
-            if hb is not None:
+            if self._mahony is not None:
+                if self._mahony_every_tick:
+                    self._mahony.refresh(self.control_dt)
+                    if self._body is not None and self._body_every_tick:
+                        self._body.refresh(self.control_dt)
+                if self._deform is not None and self._deform_every_tick:
+                    self._deform.refresh(self.imu_quat)
+            elif hb is not None:
                 hb.mahony_filter(self.imu_quat, self._omega, self._cf, self._bias,
                                  self.mahony_kp, self.mahony_ki, self.control_dt)
                 if self._deform is not None and self._deform_every_tick:
@@ -775,12 +837,27 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                 imu = self.engine.sensor_measurements["ImuSensor"]     # (6, n_imu, B)
                 blocks.mahony_filter(self.imu_quat, self._omega, self._cf, imu[:3], imu[3:], self._bias,
                                      self.mahony_kp, self.mahony_ki, self.control_dt)
+        if self._mahony is not None and not self._mahony_every_tick:
+            self._mahony.refresh(self.step_dt)
+        if self._body is not None and not (self._mahony_every_tick and self._body_every_tick):
+            self._body.refresh(self.step_dt)
         if self._deform is not None and not self._deform_every_tick:
             self._deform.refresh(self.imu_quat)
+
+    @staticmethod
+    def _observer_features(block: Any) -> Dict[str, torch.Tensor]:
+        out = {"quat": block.quat.permute(2, 0, 1), "omega": block.omega.permute(2, 0, 1)}
+        if block.rpy is not None:
+            out["rpy"] = block.rpy.permute(2, 0, 1)
+        return out
 
     def observation(self) -> ObsType:
         obs = super().observation()
         obs["features"] = {"mahony_filter": self.imu_quat.permute(2, 0, 1)}
+        if self._mahony is not None:
+            obs["features"]["mahony_filter"] = self._observer_features(self._mahony)
+        if self._body is not None:
+            obs["features"]["body_observer"] = self._observer_features(self._body)
         if self._deform is not None:
             est = {"quat": self._deform.quat.permute(2, 0, 1)}
             if self._deform.rpy is not None:
