@@ -19,11 +19,10 @@ from typing import Any, Dict, List, Sequence, Tuple, Union
 import numpy as np
 
 from . import _abi
-from .model import (JT_FREEFLYER, JT_PU, JT_PX, JT_RU, JT_RUBU, JT_RUBX, JT_RUBY, JT_RUBZ, JT_RX, JT_RY, JT_RZ, JT_SPHERICAL,
-                    CompiledModel)
+from ._plan import (AXIS_KIND, SEG_AXIS, SEG_NONE, SEG_QUAT, SEG_UNBOUNDED, SEG_X, SEG_Y, SEG_Z, SegmentTable,  # noqa: F401
+                    fill_desc)
+from .model import JT_FREEFLYER, JT_PU, JT_PX, JT_RUBU, JT_RUBX, JT_RUBY, JT_RUBZ, JT_SPHERICAL, CompiledModel
 
-# joint kinds of a plan segment (include/jiminy_hip.h, jm_attitude_desc)
-SEG_NONE, SEG_X, SEG_Y, SEG_Z, SEG_AXIS, SEG_UNBOUNDED, SEG_QUAT = 0, 1, 2, 3, 4, 5, 6
 TWIST_KEEP, TWIST_REMOVE, TWIST_INTEGRATE = 0, 1, 2
 
 
@@ -75,18 +74,11 @@ class AttitudePlan:
 def make_desc(*, nq: int, kp, ki, rel_quat, frame_seg_start, seg_kind, seg_q_index, seg_rot, seg_axis
               ) -> Tuple["_abi.AttitudeDesc", List[np.ndarray]]:
     """`jm_attitude_desc` from plain arrays (layout: include/jiminy_hip.h); the second value keeps them alive."""
-    import ctypes as C
-    i32 = lambda x: np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)      # noqa: E731
-    f64 = lambda x: np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float64)    # noqa: E731
-    ints = {k: i32(v) for k, v in dict(frame_seg_start=frame_seg_start, seg_kind=seg_kind, seg_q_index=seg_q_index).items()}
-    dbls = {k: f64(v) for k, v in dict(kp=kp, ki=ki, rel_quat=rel_quat, seg_rot=seg_rot, seg_axis=seg_axis).items()}
     d = _abi.AttitudeDesc()
-    d.n_imu, d.nq, d.n_seg = len(dbls["kp"]), int(nq), len(ints["seg_kind"])
-    for k, a in ints.items():
-        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_int32)))
-    for k, a in dbls.items():
-        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_double)))
-    return d, list(ints.values()) + list(dbls.values())
+    a, keep = fill_desc(d, dict(frame_seg_start=frame_seg_start, seg_kind=seg_kind, seg_q_index=seg_q_index),
+                        dict(kp=kp, ki=ki, rel_quat=rel_quat, seg_rot=seg_rot, seg_axis=seg_axis))
+    d.n_imu, d.nq, d.n_seg = len(a["kp"]), int(nq), len(a["seg_kind"])
+    return d, keep
 
 
 def build_plan(model: CompiledModel, kp: Union[np.ndarray, Sequence[float], float] = 1.0,
@@ -97,49 +89,27 @@ def build_plan(model: CompiledModel, kp: Union[np.ndarray, Sequence[float], floa
         raise ValueError("the attitude observers need at least one ImuSensor")
     n_imu = len(sensors)
     kp, ki = broadcast_gain(kp, n_imu), broadcast_gain(ki, n_imu)
-    seg_kind: List[int] = []
-    seg_q: List[int] = []
-    seg_rot: List[np.ndarray] = []
-    seg_axis: List[np.ndarray] = []
-    frame_seg_start = [0]
+    segs = SegmentTable()
+
+    def joint_segment(j: int):
+        t, iq = int(model.jtypes[j]), int(model.idx_q[j])
+        if t in AXIS_KIND:
+            return AXIS_KIND[t], iq, model.axes[j], 0.0
+        if t in (JT_RUBX, JT_RUBY, JT_RUBZ, JT_RUBU):
+            return SEG_UNBOUNDED, iq, model.axes[j] if t == JT_RUBU else np.eye(3)[t - JT_RUBX], 0.0
+        if t == JT_SPHERICAL:
+            return SEG_QUAT, iq, np.zeros(3), 0.0
+        if t == JT_FREEFLYER:
+            return SEG_QUAT, iq + 3, np.zeros(3), 0.0
+        if not JT_PX <= t <= JT_PU:
+            raise NotImplementedError(f"joint type {t} of joint '{model.joint_names[j]}'")
+        return None
+
     rel_quat = []
-    axis_kind = {JT_RX: SEG_X, JT_RY: SEG_Y, JT_RZ: SEG_Z, JT_RU: SEG_AXIS}
     for s in sensors:
         fr = model.frame(s["frame"])
         rel_quat.append(matrix_to_quat(np.asarray(fr.R, dtype=np.float64)))
-        path, j = [], int(fr.parent_joint)
-        while j != 0:
-            path.append(j)
-            j = int(model.parents[j])
-        const = np.eye(3)
-
-        def joint(kind: int, q_index: int, axis) -> None:
-            nonlocal const
-            seg_kind.append(kind)
-            seg_q.append(q_index)
-            seg_rot.append(const)
-            seg_axis.append(np.asarray(axis, dtype=np.float64))
-            const = np.eye(3)
-        for j in reversed(path):
-            const = const @ model.placement_R[j]
-            t, iq = int(model.jtypes[j]), int(model.idx_q[j])
-            if t in axis_kind:
-                joint(axis_kind[t], iq, model.axes[j])
-            elif t in (JT_RUBX, JT_RUBY, JT_RUBZ, JT_RUBU):
-                joint(SEG_UNBOUNDED, iq, model.axes[j] if t == JT_RUBU else np.eye(3)[t - JT_RUBX])
-            elif t == JT_SPHERICAL:
-                joint(SEG_QUAT, iq, np.zeros(3))
-            elif t == JT_FREEFLYER:
-                joint(SEG_QUAT, iq + 3, np.zeros(3))
-            elif not JT_PX <= t <= JT_PU:
-                raise NotImplementedError(f"joint type {t} of joint '{model.joint_names[j]}'")
-        const = const @ np.asarray(fr.R, dtype=np.float64)
-        if len(seg_kind) == frame_seg_start[-1] or not np.array_equal(const, np.eye(3)):
-            seg_kind.append(SEG_NONE)
-            seg_q.append(-1)
-            seg_rot.append(const)
-            seg_axis.append(np.zeros(3))
-        frame_seg_start.append(len(seg_kind))
-    arrays = dict(nq=int(model.nq), kp=kp, ki=ki, rel_quat=np.array(rel_quat), frame_seg_start=frame_seg_start, seg_kind=seg_kind,
-                  seg_q_index=seg_q, seg_rot=np.array(seg_rot), seg_axis=np.array(seg_axis))
+        segs.add_frame(model, int(fr.parent_joint), fr.R, joint_segment)
+    arrays = dict(nq=int(model.nq), kp=kp, ki=ki, rel_quat=np.array(rel_quat), frame_seg_start=segs.frame_seg_start,
+                  seg_kind=segs.kind, seg_q_index=segs.index, seg_rot=np.array(segs.rot), seg_axis=np.array(segs.axis))
     return AttitudePlan(imu_names=[s["name"] for s in sensors], kp=kp, ki=ki, rel_quat=np.array(rel_quat), arrays=arrays)

@@ -358,7 +358,8 @@ def write_header(model: CompiledModel) -> str:
 def _sources() -> List[str]:
     return [os.path.join(CSRC, n) for n in ("jm_lib.cpp", "jm_kernels.h", "jm_math.h", "jm_quad.h",
                                             "jm_pack.h", "jm_adaptive.h", "jm_blocks.h", "jm_deform.h", "jm_attitude.h", "jm_random.h",
-                                            "jm_constraint.h", "jm_qcon.h", "jm_qtip.h", "jm_qdopri.h", "jm_lib_constraint.cpp")] + \
+                                            "jm_constraint.h", "jm_qcon.h", "jm_qtip.h", "jm_qdopri.h", "jm_lib_constraint.cpp",
+                                            "jm_lib_blocks.cpp", "jm_rotation.h", "jm_error.h")] + \
            [os.path.join(CSRC, "..", "..", "include", "jiminy_hip.h"), os.path.join(CSRC, "jm_dispatch.h")]
 
 
@@ -446,8 +447,8 @@ def build_library(model: CompiledModel, force: bool = False, verbose: bool = Fal
         raise RuntimeError(
             f"hipcc not found ({HIPCC}); cannot build the HIP library for topology "
             f"{model.topology_hash()} and no prebuilt {lib} exists")
-    # up to five translation units compiled in parallel (the constraint-model kernels are the longest single compiles
-    # of a large topology), then linked into one shared library
+    # the translation units are compiled in parallel (the constraint-model kernels are the longest single compiles of a
+    # large topology; the topology-independent blocks have a unit of their own), then linked into one shared library
     common = COMMON_FLAGS + [f"-DJM_TOPO_HEADER=\"{hdr}\""]
     common += list(BUILD_VARIANTS[v])
     common += extra_flags or []
@@ -457,11 +458,12 @@ def build_library(model: CompiledModel, force: bool = False, verbose: bool = Fal
     parts = [1, 2, 3, 4, 5, 6, 11, 12] if quad_structure(model) is not None else [1, 15, 16]
     if qcon_split(model):
         parts += [7, 8, 9, 10, 13, 14]
-    objs = [lib + ".main.o"] + [lib + f".part{p}.o" for p in parts]
-    cmds = [[HIPCC] + common + ["-DJM_SPLIT_CONSTRAINT", "-c", os.path.join(CSRC, "jm_lib.cpp"), "-o", objs[0]]]
+    objs = [lib + ".main.o", lib + ".blocks.o"] + [lib + f".part{p}.o" for p in parts]
+    cmds = [[HIPCC] + common + ["-DJM_SPLIT_CONSTRAINT", "-c", os.path.join(CSRC, "jm_lib.cpp"), "-o", objs[0]],
+            [HIPCC] + common + ["-c", os.path.join(CSRC, "jm_lib_blocks.cpp"), "-o", objs[1]]]
     pf = part_flags(model)
     cmds += [[HIPCC] + common + pf.get(str(p), []) + [f"-DJM_CON_PART={p}", "-c", os.path.join(CSRC, "jm_lib_constraint.cpp"), "-o", o]
-             for p, o in zip(parts, objs[1:])]
+             for p, o in zip(parts, objs[2:])]
     if verbose:
         for c in cmds:
             print(" ".join(c))

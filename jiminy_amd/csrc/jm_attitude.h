@@ -1,7 +1,7 @@
 // jm_attitude.h -- the attitude observers of gym_jiminy as batched HIP kernels: what the `MahonyFilter` class does around
-// its numba function (per-IMU gains, twist removal, Euler angles, initialisation at the first refresh of an episode) and
-// the `BodyObserver` block.  Every lane is one environment, arrays are `[rows][B]` like the physics state and the blocks
-// of jm_blocks.h / jm_deform.h, whose per-lane functions (`deform_swing`, `deform_mat_to_quat`, `deform_qmul`) are used here.
+// its numba function (per-IMU gains, twist removal, Euler angles, initialisation at the first refresh of an episode), that
+// function on its own, and the `BodyObserver` block.  Every lane is one environment, arrays are `[rows][B]` like the physics
+// state and the blocks of jm_blocks.h; the quaternion functions and the segment record are those of jm_rotation.h.
 //
 // Reference (numba / numpy code restated here per lane):
 //   MahonyFilter.refresh_observation   python/gym_jiminy/common/gym_jiminy/common/blocks/mahony_filter.py:337-393
@@ -9,13 +9,10 @@
 //   BodyObserver.refresh_observation   python/gym_jiminy/common/gym_jiminy/common/blocks/body_orientation_observer.py:237-266
 //   update_twist                       body_orientation_observer.py:26-71
 //   remove_twist_from_quat             python/gym_jiminy/common/gym_jiminy/common/utils/math.py:1202-1244
-//   compute_tilt_from_quat             utils/math.py:1045-1060
-//   swing_from_vector                  utils/math.py:1066-1133
-//   quat_multiply / quat_apply         utils/math.py:570-626 / 645-709
-//   matrices_to_quat / quat_to_rpy     utils/math.py:306-360 / 158-201
+//   quat_apply                         utils/math.py:645-709
 // `swing_from_vector` on the IMUs of one environment decides its singular branch with `np.any` over them: the flag handed to
-// `deform_swing` is "any IMU of the lane" (jm_deform.h: each IMU then takes the scalar branch and is normalised twice).  The
-// undefined `esp_ratio` case is handled as documented at the top of jm_deform.h.
+// it is "any IMU of the lane".  The three observer kernels take the tilt in its TILT_ROUNDED form, the plain function in its
+// TILT_FUSED form (jm_rotation.h).
 //
 // The true IMU orientations of the exact initialisation (the reference reads `oMf` of pinocchio, :357-366) are a
 // rotation-only walk from the root to the sensor frame over the lane's `q` rows: per IMU a list of segments (constant
@@ -26,17 +23,16 @@
 #include <string>
 #include <vector>
 
-#include "jm_deform.h"
+#include "jm_rotation.h"
+#include "../../include/jiminy_hip.h"
 
 namespace jm
 {
 // ---- the packed plan: `it` (int32) = [n_imu, offset of the segment ints, n_imu x (first segment, segment count),
-// n_seg x (kind, q index)]; `dt` (float64) = n_imu x (kp, ki, rel_quat xyzw), then per segment 9 rotation entries and 3
-// axis entries.
+// segment ints]; `dt` (float64) = n_imu x (kp, ki, rel_quat xyzw), then the segments of jm_rotation.h (index = first row of
+// `q`, no ratio).
 constexpr int ATT_IMU_DOUBLES = 6;
-constexpr int ATT_SEG_DOUBLES = 12;
 constexpr int ATT_MAX_SEGS_PER_IMU = 256;
-constexpr int ATT_SEG_NONE = 0, ATT_SEG_AXIS = 4, ATT_SEG_UNBOUNDED = 5, ATT_SEG_QUAT = 6;
 
 // Validate a description and pack it.  Returns false and a message on a malformed description.
 inline bool attitude_pack(const jm_attitude_desc * d, std::vector<int32_t> & it, std::vector<double> & dt, std::string & why)
@@ -62,9 +58,9 @@ inline bool attitude_pack(const jm_attitude_desc * d, std::vector<int32_t> & it,
     for (int s = 0; s < d->n_seg; ++s)
     {
         const int kind = d->seg_kind[s], qi = d->seg_q_index[s];
-        if (kind < 0 || kind > ATT_SEG_QUAT)
+        if (kind < 0 || kind > SEG_QUAT)
         { why = "jm_attitude_plan_create: segment " + std::to_string(s) + " has an unknown joint kind"; return false; }
-        const int rows = kind == ATT_SEG_NONE ? 0 : (kind == ATT_SEG_QUAT ? 4 : (kind == ATT_SEG_UNBOUNDED ? 2 : 1));
+        const int rows = kind == SEG_NONE ? 0 : (kind == SEG_QUAT ? 4 : (kind == SEG_UNBOUNDED ? 2 : 1));
         if (rows && (qi < 0 || qi + rows > d->nq))
         { why = "jm_attitude_plan_create: segment " + std::to_string(s) + " reads q rows [" + std::to_string(qi) + ", " +
                 std::to_string(qi + rows) + ") out of range [0, " + std::to_string(d->nq) + ")"; return false; }
@@ -77,58 +73,15 @@ inline bool attitude_pack(const jm_attitude_desc * d, std::vector<int32_t> & it,
         it.push_back(d->frame_seg_start[s]);
         it.push_back(d->frame_seg_start[s + 1] - d->frame_seg_start[s]);
     }
-    for (int s = 0; s < d->n_seg; ++s) { it.push_back(d->seg_kind[s]); it.push_back(d->seg_kind[s] ? d->seg_q_index[s] : 0); }
-    dt.assign((size_t)d->n_imu * ATT_IMU_DOUBLES + (size_t)d->n_seg * ATT_SEG_DOUBLES, 0.0);
+    dt.clear();
     for (int s = 0; s < d->n_imu; ++s)
     {
-        double * o = dt.data() + (size_t)s * ATT_IMU_DOUBLES;
-        o[0] = d->kp[s];
-        o[1] = d->ki[s];
-        for (int k = 0; k < 4; ++k) o[2 + k] = d->rel_quat[4 * s + k];
+        dt.push_back(d->kp[s]);
+        dt.push_back(d->ki[s]);
+        dt.insert(dt.end(), d->rel_quat + 4 * s, d->rel_quat + 4 * s + 4);
     }
-    for (int s = 0; s < d->n_seg; ++s)
-    {
-        double * o = dt.data() + (size_t)d->n_imu * ATT_IMU_DOUBLES + (size_t)s * ATT_SEG_DOUBLES;
-        for (int k = 0; k < 9; ++k) o[k] = d->seg_rot[9 * s + k];
-        for (int k = 0; k < 3; ++k) o[9 + k] = d->seg_axis[3 * s + k];
-    }
+    pack_segments(d->n_seg, d->seg_kind, d->seg_q_index, d->seg_rot, d->seg_axis, nullptr, it, dt);
     return true;
-}
-
-// `compute_tilt_from_quat` (utils/math.py:1056-1059).  Near the singular branch of `swing_from_vector` one ulp of v_z is
-// amplified by 1e5, so the three lines are evaluated as written: every product is rounded on its own.  The library is
-// built with -ffp-contract=fast, under which the backend fuses a multiply into the following add whatever a pragma says;
-// passing each product through an empty asm statement keeps it a value of its own (no instruction is emitted for it).
-template<class T> JM_DEV T attitude_rounded(T x)
-{
-#ifndef JM_HOST_EMU
-    asm volatile("" : "+v"(x));
-#endif
-    return x;
-}
-template<class T> JM_DEV V3<T> attitude_tilt(const Quat<T> & q)
-{
-    const T xz = attitude_rounded(q.x * q.z), yw = attitude_rounded(q.y * q.w);
-    const T yz = attitude_rounded(q.y * q.z), wx = attitude_rounded(q.w * q.x);
-    const T xx = attitude_rounded(q.x * q.x), yy = attitude_rounded(q.y * q.y);
-    return {T(2) * (xz - yw), T(2) * (yz + wx), T(1) - T(2) * (xx + yy)};
-}
-
-template<class T> JM_DEV void attitude_store_quat(T * __restrict__ quat, long long nB, long long o, const Quat<T> & q)
-{
-    quat[o] = q.x; quat[nB + o] = q.y; quat[2 * nB + o] = q.z; quat[3 * nB + o] = q.w;
-}
-
-// `quat_to_rpy` (utils/math.py:182-197)
-template<class T> JM_DEV void attitude_store_rpy(T * __restrict__ rpy, long long nB, long long o, const Quat<T> & e)
-{
-    const T xx = e.x * e.x, xy = e.x * e.y, xw = e.x * e.w;
-    const T yy = e.y * e.y, yz = e.y * e.z, zz = e.z * e.z, zw = e.z * e.w, ww = e.w * e.w;
-    const T n2 = (T(3) - (xx + yy + zz + ww)) / T(2);
-    const T yw = e.y * e.w * n2, xz = e.x * e.z * n2;
-    rpy[o] = atan2_(T(2) * (xw + yz), T(1) - T(2) * (xx + yy));
-    rpy[nB + o] = -T(3.14159265358979323846) / T(2) + T(2) * atan2_(sqrt_(T(1) + T(2) * (yw - xz)), sqrt_(T(1) - T(2) * (yw - xz)));
-    rpy[2 * nB + o] = atan2_(T(2) * (zw + xy), T(1) - T(2) * (yy + zz));
 }
 
 // `remove_twist_from_quat` over the IMUs of one lane (in place in `quat`), then `quat_to_rpy` when `rpy` is given; with
@@ -140,18 +93,18 @@ JM_DEV void attitude_swing_and_rpy(int n_imu, bool remove_twist, T * __restrict_
     bool singular = false;
     if (remove_twist)
         for (int s = 0; s < n_imu; ++s)
-            singular |= attitude_tilt(deform_load_quat(quat, s, nB, B, lane)).z < T(-1) + T(1e-5);
+            singular |= quat_tilt<TILT_ROUNDED>(quat_load(quat, s, nB, B, lane)).z < T(-1) + T(1e-5);
     for (int s = 0; s < n_imu; ++s)
     {
         const long long o = (long long)s * B + lane;
-        Quat<T> q = deform_load_quat(quat, s, nB, B, lane);
+        Quat<T> q = quat_load(quat, s, nB, B, lane);
         if (remove_twist)
         {
-            const V3<T> v = attitude_tilt(q);
-            q = deform_swing(v.x, v.y, v.z, singular);
-            attitude_store_quat(quat, nB, o, q);
+            const V3<T> v = quat_tilt<TILT_ROUNDED>(q);
+            q = swing_from_vector(v.x, v.y, v.z, singular);
+            quat_store(quat, nB, o, q);
         }
-        if (rpy) attitude_store_rpy(rpy, nB, o, q);
+        if (rpy) quat_store_rpy(rpy, nB, o, q);
     }
 }
 
@@ -166,15 +119,15 @@ JM_DEV M3<T> attitude_frame_rot(const int32_t * __restrict__ it, const double * 
     M3<T> R = ident3<T>();
     for (int s = s0; s < s1; ++s)
     {
-        const double * d = seg + (long long)s * ATT_SEG_DOUBLES;
+        const double * d = seg + (long long)s * SEG_DOUBLES;
         const M3<T> Cm = {(T)d[0], (T)d[1], (T)d[2], (T)d[3], (T)d[4], (T)d[5], (T)d[6], (T)d[7], (T)d[8]};
         R = s == s0 ? Cm : R * Cm;
         const int kind = it[si + 2 * s];
-        if (kind == ATT_SEG_NONE) continue;
+        if (kind == SEG_NONE) continue;
         const T * qr = q + (long long)it[si + 2 * s + 1] * B + lane;
         M3<T> J;
-        if (kind == ATT_SEG_QUAT) J = quat_to_matrix<T>(qr[0], qr[B], qr[2 * B], qr[3 * B]);
-        else if (kind == ATT_SEG_UNBOUNDED) J = rot_rodrigues<T>(v3((T)d[9], (T)d[10], (T)d[11]), qr[0], qr[B]);
+        if (kind == SEG_QUAT) J = quat_to_matrix<T>(qr[0], qr[B], qr[2 * B], qr[3 * B]);
+        else if (kind == SEG_UNBOUNDED) J = rot_rodrigues<T>(v3((T)d[9], (T)d[10], (T)d[11]), qr[0], qr[B]);
         else
         {
             T sn, cs;
@@ -224,38 +177,51 @@ JM_DEV void attitude_init_lane(const int32_t * __restrict__ it, const double * _
     {
         const long long o = (long long)s * B + lane;
         Quat<T> e;
-        if (exact) e = deform_mat_to_quat(attitude_frame_rot<T>(it, dt, s, q, B, lane));
+        if (exact) e = matrix_to_quat(attitude_frame_rot<T>(it, dt, s, q, B, lane));
         else
         {
             const T * g = imu + (long long)s * 6 * B + lane;
             const T ax = g[3 * B], ay = g[4 * B], az = g[5 * B];
             const T n = sqrt_(ax * ax + ay * ay + az * az);
-            e = deform_swing(ax / n, ay / n, az / n, singular);
+            e = swing_from_vector(ax / n, ay / n, az / n, singular);
         }
-        attitude_store_quat(quat, nB, o, e);
+        quat_store(quat, nB, o, e);
         omega[o] = T(0); omega[nB + o] = T(0); omega[2 * nB + o] = T(0);
         cf[o] = T(0); cf[nB + o] = T(0); cf[2 * nB + o] = T(0);
         bias[o] = T(0); bias[nB + o] = T(0); bias[2 * nB + o] = T(0);
         if (twist) twist[o] = T(0);
-        if (rpy) attitude_store_rpy(rpy, nB, o, e);
+        if (rpy) quat_store_rpy(rpy, nB, o, e);
     }
 }
 
-// One tick of an initialised `MahonyFilter` (mahony_filter.py:376-393) for one lane: `mahony_filter` with the gains of
-// every IMU, then the twist removal and the Euler angles -- which run after the filter's early return as well.
-template<class T>
-JM_DEV void mahony_observer_lane(const double * __restrict__ dt, int n_imu, const T * __restrict__ imu, T * __restrict__ quat,
-                                 T * __restrict__ omega, T * __restrict__ cf, T * __restrict__ bias, T step, int ignore_twist,
-                                 T * __restrict__ rpy, long long B, long long lane)
+// where `mahony_filter` takes the gains of IMU s from: the two scalars of the plain function, or the plan
+template<class T> struct UniformGains
+{
+    T kp_, ki_;
+    JM_DEV T kp(int) const { return kp_; }
+    JM_DEV T ki(int) const { return ki_; }
+};
+template<class T> struct PlanGains
+{
+    const double * dt;
+    JM_DEV T kp(int s) const { return (T)dt[s * ATT_IMU_DOUBLES]; }
+    JM_DEV T ki(int s) const { return (T)dt[s * ATT_IMU_DOUBLES + 1]; }
+};
+
+// `mahony_filter` (mahony_filter.py:28-101) for one lane, F the form of the tilt.  (No `__restrict__` here: `jm_block_mahony_filter`
+// never promised it; the observer kernel's own parameters carry it.)  imu raw field `[n_imu][6][B]` (gyro 0-2, accel 3-5); quat `[4][n_imu][B]`; omega, cf, bias `[3][n_imu][B]`.
+template<TiltForm F, class T, class Gains>
+JM_DEV void mahony_lane(int n_imu, const Gains gains, const T * imu, T * quat, T * omega, T * cf, T * bias, T step, long long B,
+                        long long lane)
 {
     const long long nB = (long long)n_imu * B;
-    // pass 1: omega, cf; the filter returns early when no IMU of the environment moves
+    // pass 1: omega, cf; the reference returns early when no IMU of the environment moves
     bool moving = false;
     for (int s = 0; s < n_imu; ++s)
     {
         const long long o = (long long)s * B + lane;
-        const T kp = (T)dt[s * ATT_IMU_DOUBLES];
-        const V3<T> v = attitude_tilt(deform_load_quat(quat, s, nB, B, lane));
+        const T kp = gains.kp(s);
+        const V3<T> v = quat_tilt<F>(quat_load(quat, s, nB, B, lane));
         const T * g = imu + (long long)s * 6 * B + lane;
         const T ax = g[3 * B] / T(9.81), ay = g[4 * B] / T(9.81), az = g[5 * B] / T(9.81);
         const T mx = ay * v.z - az * v.y, my = az * v.x - ax * v.z, mz = ax * v.y - ay * v.x;
@@ -266,28 +232,38 @@ JM_DEV void mahony_observer_lane(const double * __restrict__ dt, int n_imu, cons
         const T eps = T(1e-6);
         moving |= !((cx < T(0) ? -cx : cx) < eps && (cy < T(0) ? -cy : cy) < eps && (cz < T(0) ? -cz : cz) < eps);
     }
+    if (!moving) return;
     // pass 2: integrate the orientation, update the bias estimate
-    if (moving)
-        for (int s = 0; s < n_imu; ++s)
-        {
-            const long long o = (long long)s * B + lane;
-            const T ki = (T)dt[s * ATT_IMU_DOUBLES + 1];
-            const T cx = cf[o], cy = cf[nB + o], cz = cf[2 * nB + o];
-            const T theta = sqrt_(cx * cx + cy * cy + cz * cz);
-            const T half = theta * (step / T(2));
-            T sh, ch;
-            sincos_(half, &sh, &ch);
-            const T px = cx / theta * sh, py = cy / theta * sh, pz = cz / theta * sh, pw = ch;
-            const Quat<T> p = deform_load_quat(quat, s, nB, B, lane);
-            const Quat<T> n = {p.x * pw + p.w * px - p.z * py + p.y * pz, p.y * pw + p.z * px + p.w * py - p.x * pz,
-                               p.z * pw - p.y * px + p.x * py + p.w * pz, p.w * pw - p.x * px - p.y * py - p.z * pz};
-            attitude_store_quat(quat, nB, o, deform_renorm(n));
-            const V3<T> v = attitude_tilt(p);
-            const T * g = imu + (long long)s * 6 * B + lane;
-            const T ax = g[3 * B] / T(9.81), ay = g[4 * B] / T(9.81), az = g[5 * B] / T(9.81);
-            const T mx = ay * v.z - az * v.y, my = az * v.x - ax * v.z, mz = ax * v.y - ay * v.x;
-            bias[o] -= ki * step * mx; bias[nB + o] -= ki * step * my; bias[2 * nB + o] -= ki * step * mz;
-        }
+    for (int s = 0; s < n_imu; ++s)
+    {
+        const long long o = (long long)s * B + lane;
+        const T ki = gains.ki(s);
+        const T cx = cf[o], cy = cf[nB + o], cz = cf[2 * nB + o];
+        const T theta = sqrt_(cx * cx + cy * cy + cz * cz);
+        const T half = theta * (step / T(2));
+        T sh, ch;
+        sincos_(half, &sh, &ch);
+        const T px = cx / theta * sh, py = cy / theta * sh, pz = cz / theta * sh, pw = ch;
+        const Quat<T> p = quat_load(quat, s, nB, B, lane);
+        const Quat<T> n = {p.x * pw + p.w * px - p.z * py + p.y * pz, p.y * pw + p.z * px + p.w * py - p.x * pz,
+                           p.z * pw - p.y * px + p.x * py + p.w * pz, p.w * pw - p.x * px - p.y * py - p.z * pz};
+        quat_store(quat, nB, o, quat_renorm(n));
+        const V3<T> v = quat_tilt<F>(p);
+        const T * g = imu + (long long)s * 6 * B + lane;
+        const T ax = g[3 * B] / T(9.81), ay = g[4 * B] / T(9.81), az = g[5 * B] / T(9.81);
+        const T mx = ay * v.z - az * v.y, my = az * v.x - ax * v.z, mz = ax * v.y - ay * v.x;
+        bias[o] -= ki * step * mx; bias[nB + o] -= ki * step * my; bias[2 * nB + o] -= ki * step * mz;
+    }
+}
+
+// One tick of an initialised `MahonyFilter` (mahony_filter.py:376-393) for one lane: `mahony_filter` with the gains of
+// every IMU, then the twist removal and the Euler angles -- which run after the filter's early return as well.
+template<class T>
+JM_DEV void mahony_observer_lane(const double * __restrict__ dt, int n_imu, const T * __restrict__ imu, T * __restrict__ quat,
+                                 T * __restrict__ omega, T * __restrict__ cf, T * __restrict__ bias, T step, int ignore_twist,
+                                 T * __restrict__ rpy, long long B, long long lane)
+{
+    mahony_lane<TILT_ROUNDED>(n_imu, PlanGains<T>{dt}, imu, quat, omega, cf, bias, step, B, lane);
     if (ignore_twist || rpy) attitude_swing_and_rpy<T>(n_imu, ignore_twist != 0, quat, rpy, B, lane);
 }
 
@@ -307,9 +283,9 @@ JM_DEV void body_observer_lane(const double * __restrict__ dt, int n_imu, const 
         const long long o = (long long)s * B + lane;
         const double * d = dt + s * ATT_IMU_DOUBLES + 2;
         const Quat<T> rel = {(T)d[0], (T)d[1], (T)d[2], (T)d[3]};
-        const Quat<T> e = deform_qmul(deform_load_quat(imu_quat, s, nB, B, lane), rel, T(1), T(-1));
-        if (twist_mode) singular |= attitude_tilt(e).z < T(-1) + T(1e-5);
-        attitude_store_quat(quat, nB, o, e);
+        const Quat<T> e = quat_mul(quat_load(imu_quat, s, nB, B, lane), rel, T(1), T(-1));
+        if (twist_mode) singular |= quat_tilt<TILT_ROUNDED>(e).z < T(-1) + T(1e-5);
+        quat_store(quat, nB, o, e);
         // `quat_apply` (utils/math.py:687-705)
         const T xx = rel.x * rel.x, xy = rel.x * rel.y, xz = rel.x * rel.z, xw = rel.x * rel.w;
         const T yy = rel.y * rel.y, yz = rel.y * rel.z, yw = rel.y * rel.w, zz = rel.z * rel.z, zw = rel.z * rel.w, ww = rel.w * rel.w;
@@ -328,9 +304,9 @@ JM_DEV void body_observer_lane(const double * __restrict__ dt, int n_imu, const 
     for (int s = 0; s < n_imu; ++s)
     {
         const long long o = (long long)s * B + lane;
-        Quat<T> e = deform_load_quat(quat, s, nB, B, lane);
-        const V3<T> v = attitude_tilt(e);
-        e = deform_swing(v.x, v.y, v.z, singular);
+        Quat<T> e = quat_load(quat, s, nB, B, lane);
+        const V3<T> v = quat_tilt<TILT_ROUNDED>(e);
+        e = swing_from_vector(v.x, v.y, v.z, singular);
         if (twist_mode == 2)
         {
             const T dtwist = (-e.y * omega[o] + e.x * omega[nB + o]) / e.w + omega[2 * nB + o];
@@ -341,12 +317,21 @@ JM_DEV void body_observer_lane(const double * __restrict__ dt, int n_imu, const 
             sincos_(T(0.5) * tw, &pz, &pw);
             e = {pw * e.x - pz * e.y, pz * e.x + pw * e.y, pz * e.w, pw * e.w};
         }
-        attitude_store_quat(quat, nB, o, e);
-        if (rpy) attitude_store_rpy(rpy, nB, o, e);
+        quat_store(quat, nB, o, e);
+        if (rpy) quat_store_rpy(rpy, nB, o, e);
     }
 }
 
 #ifndef JM_HOST_EMU
+template<class T>
+__global__ void __launch_bounds__(256) k_mahony(int n_imu, const T * imu, T * quat, T * omega, T * cf, T * bias,
+                                                 double kp, double ki, double dt, long long B)
+{
+    const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (lane >= B) return;
+    mahony_lane<TILT_FUSED>(n_imu, UniformGains<T>{(T)kp, (T)ki}, imu, quat, omega, cf, bias, (T)dt, B, lane);
+}
+
 struct AttitudeArgs
 {
     const int32_t * it;

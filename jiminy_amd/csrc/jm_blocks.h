@@ -4,8 +4,7 @@
 // Reference (numba kernels restated here, scalar branches become per-lane selects):
 //   integrate_zoh   python/gym_jiminy/common/gym_jiminy/common/blocks/proportional_derivative_controller.py:23-98
 //   pd_controller   proportional_derivative_controller.py:101-163
-//   mahony_filter   python/gym_jiminy/common/gym_jiminy/common/blocks/mahony_filter.py:28-101
-//   compute_tilt_from_quat  python/gym_jiminy/common/gym_jiminy/common/utils/math.py:1046-1060
+// (`mahony_filter` is with the attitude observers, jm_attitude.h)
 // One launch replaces the ~40 elementwise tensor kernels the same block costs as a tensor
 // program; the blocks are HBM-bound (PD: 96 scalars per lane in, 48 out for 12 motors).
 #pragma once
@@ -79,57 +78,6 @@ __global__ void __launch_bounds__(256) k_pd_controller(const PdParams p, const T
     }
 }
 
-// imu raw field: [n_imu][6][B] (gyro 0-2, accel 3-5); quat: [4][n_imu][B]; omega, cf, bias: [3][n_imu][B]
-template<class T>
-__global__ void __launch_bounds__(256) k_mahony(int n_imu, const T * imu, T * quat, T * omega, T * cf, T * bias,
-                                                 double kp_, double ki_, double dt_, long long B)
-{
-    const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (lane >= B) return;
-    const T kp = (T)kp_, ki = (T)ki_, dt = (T)dt_;
-    const long long nB = (long long)n_imu * B;
-    // pass 1: omega, cf; the reference returns early when no IMU of the environment moves
-    bool moving = false;
-    for (int s = 0; s < n_imu; ++s)
-    {
-        const long long o = (long long)s * B + lane;
-        const T qx = quat[o], qy = quat[nB + o], qz = quat[2 * nB + o], qw = quat[3 * nB + o];
-        const T vx = T(2) * (qx * qz - qy * qw), vy = T(2) * (qy * qz + qw * qx), vz = T(1) - T(2) * (qx * qx + qy * qy);
-        const T * g = imu + (long long)s * 6 * B + lane;
-        const T ax = g[3 * B] / T(9.81), ay = g[4 * B] / T(9.81), az = g[5 * B] / T(9.81);
-        const T mx = ay * vz - az * vy, my = az * vx - ax * vz, mz = ax * vy - ay * vx;
-        const T ox = g[0] - bias[o], oy = g[B] - bias[nB + o], oz = g[2 * B] - bias[2 * nB + o];
-        omega[o] = ox; omega[nB + o] = oy; omega[2 * nB + o] = oz;
-        const T cx = ox + kp * mx, cy = oy + kp * my, cz = oz + kp * mz;
-        cf[o] = cx; cf[nB + o] = cy; cf[2 * nB + o] = cz;
-        const T eps = T(1e-6);
-        moving |= !((cx < T(0) ? -cx : cx) < eps && (cy < T(0) ? -cy : cy) < eps && (cz < T(0) ? -cz : cz) < eps);
-    }
-    if (!moving) return;
-    // pass 2: integrate the orientation, update the bias estimate
-    for (int s = 0; s < n_imu; ++s)
-    {
-        const long long o = (long long)s * B + lane;
-        const T cx = cf[o], cy = cf[nB + o], cz = cf[2 * nB + o];
-        const T theta = sqrt_(cx * cx + cy * cy + cz * cz);
-        const T half = theta * (dt / T(2));
-        T sh, ch;
-        sincos_(half, &sh, &ch);
-        const T px = cx / theta * sh, py = cy / theta * sh, pz = cz / theta * sh, pw = ch;
-        const T qx = quat[o], qy = quat[nB + o], qz = quat[2 * nB + o], qw = quat[3 * nB + o];
-        T nx = qx * pw + qw * px - qz * py + qy * pz;
-        T ny = qy * pw + qz * px + qw * py - qx * pz;
-        T nz = qz * pw - qy * px + qx * py + qw * pz;
-        T nw = qw * pw - qx * px - qy * py - qz * pz;
-        const T k = (T(3) - (nx * nx + ny * ny + nz * nz + nw * nw)) / T(2);
-        quat[o] = nx * k; quat[nB + o] = ny * k; quat[2 * nB + o] = nz * k; quat[3 * nB + o] = nw * k;
-        const T * g = imu + (long long)s * 6 * B + lane;
-        const T vx = T(2) * (qx * qz - qy * qw), vy = T(2) * (qy * qz + qw * qx), vz = T(1) - T(2) * (qx * qx + qy * qy);
-        const T ax = g[3 * B] / T(9.81), ay = g[4 * B] / T(9.81), az = g[5 * B] / T(9.81);
-        const T mx = ay * vz - az * vy, my = az * vx - ax * vz, mz = ax * vy - ay * vx;
-        bias[o] -= ki * dt * mx; bias[nB + o] -= ki * dt * my; bias[2 * nB + o] -= ki * dt * mz;
-    }
-}
 // ---- PDAdapter: `pd_adapter` (proportional_derivative_controller.py:166-260), once per environment step.
 // action [M][B]; command_state [3][M][B] (position, velocity, acceleration targets); out [M][B] = the target
 // acceleration the PD controller holds over the step.  deadband[m] < 0: none.

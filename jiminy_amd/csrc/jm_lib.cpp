@@ -10,10 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <new>
-#include <random>
 #include <string>
 #include <vector>
 
@@ -26,13 +23,10 @@
 #include "jm_constraint.h"
 #include "jm_qcon.h"
 #include "jm_pack.h"
-#include "jm_blocks.h"
-#include "jm_deform.h"
-#include "jm_attitude.h"
 #include "jm_adaptive.h"
 #include "jm_qdopri.h"
-#include "jm_random.h"
 #include "jm_dispatch.h"
+#include "jm_error.h"
 
 #define JM_ABI_VERSION 11
 
@@ -68,24 +62,6 @@ extern template __global__ void k_qtip_exact<double, Topo>(const QConArgs<double
 #endif
 }
 #endif
-
-namespace
-{
-thread_local std::string g_last_error;
-
-int32_t fail(int32_t code, const std::string & msg)
-{
-    g_last_error = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                              \
-    do                                                                                             \
-    {                                                                                              \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(JM_ERUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
-}  // namespace
 
 struct jm_model
 {
@@ -938,436 +914,6 @@ int32_t jm_batch_timing_summary(jm_batch * b, int32_t * n_launches, double * tot
     *n_launches = (int32_t)b->n_timed;
     *total_ms = sum;
     b->n_timed = 0;
-    return JM_OK;
-}
-
-int32_t jm_block_pd_controller(int32_t dtype, int64_t B, int32_t M, const void * encoder,
-                               const int32_t * encoder_index, void * command_state, const double * lower,
-                               const double * upper, const double * kp, const double * kd,
-                               const double * effort_limit, double control_dt, void * out_torque, void * stream)
-{
-    if (!encoder || !encoder_index || !command_state || !lower || !upper || !kp || !kd || !effort_limit || !out_torque)
-        return fail(JM_EINVAL, "jm_block_pd_controller: null argument");
-    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_pd_controller: bad sizes");
-    if (control_dt < 0.0) return fail(JM_EINVAL, "Integration backward in time is not supported.");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_pd_controller: bad dtype");
-    jm::PdParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.M = M;
-    p.dt = control_dt;
-    for (int m = 0; m < M; ++m)
-    {
-        p.enc_index[m] = encoder_index[m];
-        for (int k = 0; k < 3; ++k) { p.lo[k][m] = lower[k * M + m]; p.hi[k][m] = upper[k * M + m]; }
-        p.kp[m] = kp[m]; p.kd[m] = kd[m]; p.effort_limit[m] = effort_limit[m];
-    }
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_pd_controller<double>), dim3(grid), dim3(256), 0, s, p, (const double *)encoder,
-                           (double *)command_state, (double *)out_torque, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_pd_controller<float>), dim3(grid), dim3(256), 0, s, p, (const float *)encoder,
-                           (float *)command_state, (float *)out_torque, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_mahony_filter(int32_t dtype, int64_t B, int32_t n_imu, const void * imu, void * quat, void * omega,
-                               void * cf, void * bias, double kp, double ki, double dt, void * stream)
-{
-    if (!imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_filter: null argument");
-    if (B <= 0 || n_imu <= 0) return fail(JM_EINVAL, "jm_block_mahony_filter: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_filter: bad dtype");
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_mahony<double>), dim3(grid), dim3(256), 0, s, n_imu, (const double *)imu, (double *)quat,
-                           (double *)omega, (double *)cf, (double *)bias, kp, ki, dt, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_mahony<float>), dim3(grid), dim3(256), 0, s, n_imu, (const float *)imu, (float *)quat,
-                           (float *)omega, (float *)cf, (float *)bias, kp, ki, dt, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_pd_adapter(int32_t dtype, int64_t B, int32_t M, const void * action, int32_t order, void * command_state,
-                            const double * lower, const double * upper, int32_t is_instantaneous, const double * velocity_deadband,
-                            double step_dt, void * out, void * stream)
-{
-    if (!action || !command_state || !lower || !upper || !out) return fail(JM_EINVAL, "jm_block_pd_adapter: null argument");
-    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_pd_adapter: bad sizes");
-    if (order != 0 && order != 1) return fail(JM_EINVAL, "Derivative order of the target must be either 0 or 1.");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_pd_adapter: bad dtype");
-    jm::PdAdapterParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.M = M; p.order = order; p.instantaneous = is_instantaneous != 0; p.dt = step_dt;
-    for (int m = 0; m < M; ++m)
-    {
-        for (int k = 0; k < 3; ++k) { p.lo[k][m] = lower[k * M + m]; p.hi[k][m] = upper[k * M + m]; }
-        p.deadband[m] = velocity_deadband ? velocity_deadband[m] : -1.0;
-    }
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_pd_adapter<double>), dim3(grid), dim3(256), 0, s, p, (const double *)action, (double *)command_state,
-                           (double *)out, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_pd_adapter<float>), dim3(grid), dim3(256), 0, s, p, (const float *)action, (float *)command_state,
-                           (float *)out, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_motor_safety_limit(int32_t dtype, int64_t B, int32_t M, const void * encoder, const int32_t * encoder_index,
-                                    const void * command, const double * kp, const double * kd, const double * soft_lo,
-                                    const double * soft_hi, const double * vel_lim, const double * eff_lim, void * out, void * stream)
-{
-    if (!encoder || !encoder_index || !command || !kp || !kd || !soft_lo || !soft_hi || !vel_lim || !eff_lim || !out)
-        return fail(JM_EINVAL, "jm_block_motor_safety_limit: null argument");
-    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_motor_safety_limit: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_motor_safety_limit: bad dtype");
-    jm::SafetyParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.M = M;
-    for (int m = 0; m < M; ++m)
-    {
-        p.enc_index[m] = encoder_index[m];
-        p.kp[m] = kp[m]; p.kd[m] = kd[m]; p.soft_lo[m] = soft_lo[m]; p.soft_hi[m] = soft_hi[m];
-        p.vel_lim[m] = vel_lim[m]; p.eff_lim[m] = eff_lim[m];
-    }
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_motor_safety_limit<double>), dim3(grid), dim3(256), 0, s, p, (const double *)encoder,
-                           (const double *)command, (double *)out, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_motor_safety_limit<float>), dim3(grid), dim3(256), 0, s, p, (const float *)encoder,
-                           (const float *)command, (float *)out, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-// ---- DeformationEstimator: the plan is validated, packed and uploaded once; the call is one launch
-struct jm_deform_plan
-{
-    int32_t * d_it = nullptr;
-    double * d_dt = nullptr;
-    int n_imu = 0, n_flex = 0, ignore_twist = 0;
-};
-
-int32_t jm_deform_plan_create(const jm_deform_desc * desc, jm_deform_plan ** out)
-{
-    if (!out) return fail(JM_EINVAL, "jm_deform_plan_create: null argument");
-    *out = nullptr;
-    std::vector<int32_t> it;
-    std::vector<double> dt;
-    std::string why;
-    if (!jm::deform_pack(desc, it, dt, why)) return fail(JM_EINVAL, why);
-    jm_deform_plan * p = new (std::nothrow) jm_deform_plan;
-    if (!p) return fail(JM_ERUNTIME, "out of host memory");
-    p->n_imu = desc->n_imu; p->n_flex = desc->n_flex; p->ignore_twist = desc->ignore_twist != 0;
-    hipError_t e = hipMalloc((void **)&p->d_it, it.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_dt, dt.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(p->d_it, it.data(), it.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_dt, dt.data(), dt.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)jm_deform_plan_destroy(p);
-        return fail(JM_ERUNTIME, std::string("jm_deform_plan_create: ") + hipGetErrorString(e));
-    }
-    *out = p;
-    return JM_OK;
-}
-
-int32_t jm_deform_plan_destroy(jm_deform_plan * p)
-{
-    if (!p) return JM_OK;
-    if (p->d_it) (void)hipFree(p->d_it);
-    if (p->d_dt) (void)hipFree(p->d_dt);
-    delete p;
-    return JM_OK;
-}
-
-int32_t jm_block_deformation_estimator(const jm_deform_plan * p, int32_t dtype, int64_t B, const void * encoder,
-                                       const void * imu_quat, void * out_quat, void * out_rpy, void * stream)
-{
-    if (!p || !encoder || !imu_quat || !out_quat) return fail(JM_EINVAL, "jm_block_deformation_estimator: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad dtype");
-    const jm::DeformArgs a{p->d_it, p->d_dt, p->n_imu, p->n_flex, p->ignore_twist};
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_deformation_estimator<double>), dim3(grid), dim3(256), 0, s, a, (const double *)encoder,
-                           (const double *)imu_quat, (double *)out_quat, (double *)out_rpy, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_deformation_estimator<float>), dim3(grid), dim3(256), 0, s, a, (const float *)encoder,
-                           (const float *)imu_quat, (float *)out_quat, (float *)out_rpy, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-// ---- attitude observers (MahonyFilter options, BodyObserver): one plan, three single-launch calls
-struct jm_attitude_plan
-{
-    int32_t * d_it = nullptr;
-    double * d_dt = nullptr;
-    int n_imu = 0;
-};
-
-int32_t jm_attitude_plan_create(const jm_attitude_desc * desc, jm_attitude_plan ** out)
-{
-    if (!out) return fail(JM_EINVAL, "jm_attitude_plan_create: null argument");
-    *out = nullptr;
-    std::vector<int32_t> it;
-    std::vector<double> dt;
-    std::string why;
-    if (!jm::attitude_pack(desc, it, dt, why)) return fail(JM_EINVAL, why);
-    jm_attitude_plan * p = new (std::nothrow) jm_attitude_plan;
-    if (!p) return fail(JM_ERUNTIME, "out of host memory");
-    p->n_imu = desc->n_imu;
-    hipError_t e = hipMalloc((void **)&p->d_it, it.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_dt, dt.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(p->d_it, it.data(), it.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_dt, dt.data(), dt.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)jm_attitude_plan_destroy(p);
-        return fail(JM_ERUNTIME, std::string("jm_attitude_plan_create: ") + hipGetErrorString(e));
-    }
-    *out = p;
-    return JM_OK;
-}
-
-int32_t jm_attitude_plan_destroy(jm_attitude_plan * p)
-{
-    if (!p) return JM_OK;
-    if (p->d_it) (void)hipFree(p->d_it);
-    if (p->d_dt) (void)hipFree(p->d_dt);
-    delete p;
-    return JM_OK;
-}
-
-int32_t jm_block_attitude_init(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * q, const void * imu,
-                               const uint8_t * lane_mask, int32_t exact_init, void * quat, void * omega, void * cf, void * bias,
-                               void * twist, void * rpy, void * stream)
-{
-    if (!p || !q || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_attitude_init: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_attitude_init: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_attitude_init: bad dtype");
-    const jm::AttitudeArgs a{p->d_it, p->d_dt, p->n_imu};
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_attitude_init<double>), dim3(grid), dim3(256), 0, s, a, (int)(exact_init != 0), (const double *)q,
-                           (const double *)imu, lane_mask, (double *)quat, (double *)omega, (double *)cf, (double *)bias,
-                           (double *)twist, (double *)rpy, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_attitude_init<float>), dim3(grid), dim3(256), 0, s, a, (int)(exact_init != 0), (const float *)q,
-                           (const float *)imu, lane_mask, (float *)quat, (float *)omega, (float *)cf, (float *)bias,
-                           (float *)twist, (float *)rpy, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_mahony_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu, void * quat, void * omega,
-                                 void * cf, void * bias, double dt, int32_t ignore_twist, void * rpy, void * stream)
-{
-    if (!p || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_observer: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_mahony_observer: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_observer: bad dtype");
-    const jm::AttitudeArgs a{p->d_it, p->d_dt, p->n_imu};
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_mahony_observer<double>), dim3(grid), dim3(256), 0, s, a, (const double *)imu, (double *)quat,
-                           (double *)omega, (double *)cf, (double *)bias, dt, (int)(ignore_twist != 0), (double *)rpy, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_mahony_observer<float>), dim3(grid), dim3(256), 0, s, a, (const float *)imu, (float *)quat,
-                           (float *)omega, (float *)cf, (float *)bias, dt, (int)(ignore_twist != 0), (float *)rpy, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_body_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu_quat, const void * imu_omega,
-                               void * quat, void * omega, void * twist, int32_t twist_mode, double time_constant_inv, double dt,
-                               void * rpy, void * stream)
-{
-    if (!p || !imu_quat || !imu_omega || !quat || !omega) return fail(JM_EINVAL, "jm_block_body_observer: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_body_observer: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_body_observer: bad dtype");
-    if (twist_mode < 0 || twist_mode > 2) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode must be 0, 1 or 2");
-    if (twist_mode == 2 && !twist) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode 2 needs the twist state");
-    if (quat == imu_quat) return fail(JM_EINVAL, "jm_block_body_observer: quat must not alias imu_quat");
-    const jm::AttitudeArgs a{p->d_it, p->d_dt, p->n_imu};
-    const unsigned grid = (unsigned)((B + 255) / 256);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_body_observer<double>), dim3(grid), dim3(256), 0, s, a, (const double *)imu_quat,
-                           (const double *)imu_omega, (double *)quat, (double *)omega, (double *)twist, (int)twist_mode,
-                           time_constant_inv, dt, (double *)rpy, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_body_observer<float>), dim3(grid), dim3(256), 0, s, a, (const float *)imu_quat,
-                           (const float *)imu_omega, (float *)quat, (float *)omega, (float *)twist, (int)twist_mode,
-                           time_constant_inv, dt, (float *)rpy, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-// ziggurat tables: computed once on the host (random.cc:66-96), one copy per device
-static int32_t ziggurat_tables_on_device(jm::rnd::ZigguratTables ** out)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    static std::mutex mtx;
-    static std::map<int, jm::rnd::ZigguratTables *> tables;
-    std::lock_guard<std::mutex> lock(mtx);
-    auto it = tables.find(dev);
-    if (it == tables.end())
-    {
-        jm::rnd::ZigguratTables host;
-        jm::rnd::ziggurat_tables(host);
-        jm::rnd::ZigguratTables * tab = nullptr;
-        HIP_TRY(hipMalloc((void **)&tab, sizeof(host)));
-        HIP_TRY(hipMemcpy(tab, &host, sizeof(host), hipMemcpyHostToDevice));
-        tables[dev] = tab;
-        *out = tab;
-    }
-    else *out = it->second;
-    return JM_OK;
-}
-
-int32_t jm_block_sensor_noise(int32_t dtype, int64_t B, int32_t n_sensors, int32_t n_fields, void * data,
-                              uint64_t * rng_state, const double * noise_std, const double * bias,
-                              const double * rot_bias_inv, void * stream)
-{
-    if (!data) return fail(JM_EINVAL, "jm_block_sensor_noise: null data");
-    if (B <= 0 || n_sensors <= 0 || n_fields <= 0 || n_fields > JM_NOISE_MAX_FIELDS ||
-        n_sensors * n_fields > JM_NOISE_MAX_ROWS)
-        return fail(JM_EINVAL, "jm_block_sensor_noise: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_sensor_noise: bad dtype");
-    if (noise_std && !rng_state) return fail(JM_EINVAL, "jm_block_sensor_noise: noise needs the generator states");
-    if (rot_bias_inv && (n_fields != 6 || n_sensors > JM_NOISE_MAX_ROT || !bias))
-        return fail(JM_EINVAL, "jm_block_sensor_noise: the rotation bias applies to IMU fields (6 rows) with a bias");
-    if (!noise_std && !bias) return JM_OK;
-    jm::NoiseParams p{};
-    p.n_sensors = n_sensors; p.n_fields = n_fields;
-    p.has_noise = noise_std != nullptr; p.has_bias = bias != nullptr; p.has_rot = rot_bias_inv != nullptr;
-    for (int i = 0; i < n_sensors * n_fields; ++i)
-    {
-        if (noise_std)
-        {
-            if (!(noise_std[i] >= 0.0)) return fail(JM_EINVAL, "jm_block_sensor_noise: negative noise standard deviation");
-            p.noise_std[i] = (float)noise_std[i];
-        }
-        if (bias) p.bias[i] = bias[i];
-    }
-    if (rot_bias_inv)
-        for (int s = 0; s < n_sensors; ++s)
-            for (int k = 0; k < 9; ++k) p.rot[s][k] = rot_bias_inv[9 * s + k];
-    jm::rnd::ZigguratTables * tab = nullptr;
-    {
-        const int32_t rc = ziggurat_tables_on_device(&tab);
-        if (rc != JM_OK) return rc;
-    }
-    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)n_sensors);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_sensor_noise<double>), grid, dim3(256), 0, s, p, tab, (double *)data, rng_state, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_sensor_noise<float>), grid, dim3(256), 0, s, p, tab, (float *)data, rng_state, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_sensor_delay(int32_t dtype, int64_t B, int32_t n_sensors, int32_t n_fields, void * data,
-                              const void * history, const int32_t * slot, const double * times, int32_t n_history,
-                              uint64_t * rng_state, const double * delay, const double * jitter, int32_t order,
-                              void * stream)
-{
-    if (!data) return fail(JM_EINVAL, "jm_block_sensor_delay: null data");
-    if (B <= 0 || n_sensors <= 0 || n_fields <= 0 || n_fields > JM_NOISE_MAX_FIELDS || n_sensors > JM_NOISE_MAX_ROWS)
-        return fail(JM_EINVAL, "jm_block_sensor_delay: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_sensor_delay: bad dtype");
-    if (order != 0 && order != 1)
-        return fail(JM_ENOTIMPL, "`delayInterpolationOrder` must be either 0 or 1.");  // abstract_sensor.hxx:399-403
-    if (history && (!slot || !times || n_history < 1 || n_history > JM_DELAY_MAX_HISTORY))
-        return fail(JM_EINVAL, "jm_block_sensor_delay: the history needs 1..64 samples with their slots and times");
-    if (!history && !rng_state) return JM_OK;
-    jm::DelayParams p{};
-    p.n_sensors = n_sensors; p.n_fields = n_fields; p.order = order;
-    p.has_history = history != nullptr; p.n_hist = history ? n_history : 0;
-    for (int i = 0; i < p.n_hist; ++i)
-    {
-        if (i > 0 && !(times[i] >= times[i - 1])) return fail(JM_EINVAL, "jm_block_sensor_delay: sample times must ascend");
-        p.slot[i] = slot[i];
-        p.times[i] = times[i];
-    }
-    for (int s = 0; s < n_sensors; ++s)
-    {
-        p.delay[s] = delay ? delay[s] : 0.0;
-        p.jitter[s] = jitter ? (float)jitter[s] : 0.0f;
-        if (!(p.delay[s] >= 0.0) || !(p.jitter[s] >= 0.0f)) return fail(JM_EINVAL, "jm_block_sensor_delay: negative delay or jitter");
-    }
-    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)n_sensors);
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_sensor_delay<double>), grid, dim3(256), 0, s, p, (double *)data, (const double *)history, rng_state, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_sensor_delay<float>), grid, dim3(256), 0, s, p, (float *)data, (const float *)history, rng_state, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_block_model_bias(int32_t dtype, int64_t B, int32_t njoints, int32_t first_joint, const double * nominal,
-                            const float * std4, uint64_t * rng_state, const uint8_t * mask, void * model_lane, void * stream)
-{
-    if (!nominal || !std4 || !rng_state || !model_lane) return fail(JM_EINVAL, "jm_block_model_bias: null argument");
-    if (B <= 0 || njoints < 1 || first_joint < 1 || first_joint > njoints) return fail(JM_EINVAL, "jm_block_model_bias: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_model_bias: bad dtype");
-    for (int i = 0; i < 4; ++i)
-        if (!(std4[i] >= 0.0f)) return fail(JM_EINVAL, "jm_block_model_bias: negative standard deviation");
-    jm::BiasParams p{};
-    p.njoints = njoints; p.first = first_joint;
-    p.inertia_std = std4[0]; p.mass_std = std4[1]; p.com_std = std4[2]; p.pos_std = std4[3];
-    jm::rnd::ZigguratTables * tab = nullptr;
-    const int32_t rc = ziggurat_tables_on_device(&tab);
-    if (rc != JM_OK) return rc;
-    const dim3 grid((unsigned)((B + 255) / 256));
-    const hipStream_t s = (hipStream_t)stream;
-    if (dtype == JM_F64)
-        hipLaunchKernelGGL((jm::k_model_bias<double>), grid, dim3(256), 0, s, p, tab, nominal, rng_state, mask, (double *)model_lane, (long long)B);
-    else
-        hipLaunchKernelGGL((jm::k_model_bias<float>), grid, dim3(256), 0, s, p, tab, nominal, rng_state, mask, (float *)model_lane, (long long)B);
-    HIP_TRY(hipGetLastError());
-    return JM_OK;
-}
-
-int32_t jm_engine_rng_seed(const uint32_t * seed, int64_t B, uint64_t * state_out)
-{
-    if (!seed || !state_out || B <= 0) return fail(JM_EINVAL, "jm_engine_rng_seed: bad arguments");
-    for (int64_t lane = 0; lane < B; ++lane)
-    {
-        // internal::generateState (random.hxx:20-44): two 32-bit words of the sequence, low word first
-        std::seed_seq seq{seed[lane]};
-        uint32_t w[2];
-        seq.generate(w, w + 2);
-        state_out[lane] = jm::rnd::pcg32_init((uint64_t)w[0] | ((uint64_t)w[1] << 32));
-    }
-    return JM_OK;
-}
-
-int32_t jm_sensor_rng_seed(const uint32_t * group_seed, int64_t B, int32_t n_sensors, uint64_t * state_out)
-{
-    if (!group_seed || !state_out || B <= 0 || n_sensors <= 0) return fail(JM_EINVAL, "jm_sensor_rng_seed: bad arguments");
-    std::vector<uint32_t> words((size_t)n_sensors);
-    for (int64_t lane = 0; lane < B; ++lane)
-    {
-        std::seed_seq seq{group_seed[lane]};
-        seq.generate(words.begin(), words.end());
-        for (int32_t s = 0; s < n_sensors; ++s) state_out[(size_t)s * B + lane] = jm::rnd::pcg32_init(words[s]);
-    }
     return JM_OK;
 }
 

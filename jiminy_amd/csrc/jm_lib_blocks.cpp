@@ -1,0 +1,412 @@
+// jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
+// blocks (`jm_block_*`), the plans of the two observer families and the seeding of the generators.  Compiled with the
+// flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
+// that the physics kernels of jm_lib.cpp are compiled without it.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <new>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "jm_blocks.h"
+#include "jm_deform.h"
+#include "jm_attitude.h"
+#include "jm_random.h"
+#include "jm_error.h"
+
+namespace
+{
+// The dtype switch and the launch of a one-thread-per-lane kernel: `launch(z, grid, s)` receives a zero of the scalar
+// type (like `with_dtype` of jm_lib.cpp), the grid of (B + 255) / 256 x `grid_y` blocks of 256 threads and the stream.
+template<class F> int32_t launch_lanes(int32_t dtype, int64_t B, unsigned grid_y, void * stream, F && launch)
+{
+    const dim3 grid((unsigned)((B + 255) / 256), grid_y);
+    if (dtype == JM_F64) launch(double(), grid, (hipStream_t)stream);
+    else launch(float(), grid, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return JM_OK;
+}
+
+// the two packed arrays of a plan (jm_deform.h, jm_attitude.h) on the device
+struct DevicePlan
+{
+    int32_t * it = nullptr;
+    double * dt = nullptr;
+    hipError_t upload(const std::vector<int32_t> & h_it, const std::vector<double> & h_dt)
+    {
+        hipError_t e = hipMalloc((void **)&it, h_it.size() * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&dt, h_dt.size() * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(it, h_it.data(), h_it.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dt, h_dt.data(), h_dt.size() * sizeof(double), hipMemcpyHostToDevice);
+        return e;
+    }
+    ~DevicePlan()
+    {
+        if (it) (void)hipFree(it);
+        if (dt) (void)hipFree(dt);
+    }
+};
+
+// validate and pack a description (`pack`), upload it into a new `Plan`
+template<class Plan, class Desc, class Pack> int32_t plan_create(const std::string & who, const Desc * desc, Plan ** out, Pack pack)
+{
+    if (!out) return fail(JM_EINVAL, who + ": null argument");
+    *out = nullptr;
+    std::vector<int32_t> it;
+    std::vector<double> dt;
+    std::string why;
+    if (!pack(desc, it, dt, why)) return fail(JM_EINVAL, why);
+    Plan * p = new (std::nothrow) Plan;
+    if (!p) return fail(JM_ERUNTIME, "out of host memory");
+    const hipError_t e = p->dev.upload(it, dt);
+    if (e != hipSuccess)
+    {
+        delete p;
+        return fail(JM_ERUNTIME, who + ": " + hipGetErrorString(e));
+    }
+    *out = p;
+    return JM_OK;
+}
+}  // namespace
+
+// ---- DeformationEstimator, attitude observers (MahonyFilter options, BodyObserver): a plan is validated, packed and
+// uploaded once; every call is one launch
+struct jm_deform_plan
+{
+    DevicePlan dev;
+    int n_imu = 0, n_flex = 0, ignore_twist = 0;
+};
+struct jm_attitude_plan
+{
+    DevicePlan dev;
+    int n_imu = 0;
+};
+
+extern "C"
+{
+int32_t jm_block_pd_controller(int32_t dtype, int64_t B, int32_t M, const void * encoder,
+                               const int32_t * encoder_index, void * command_state, const double * lower,
+                               const double * upper, const double * kp, const double * kd,
+                               const double * effort_limit, double control_dt, void * out_torque, void * stream)
+{
+    if (!encoder || !encoder_index || !command_state || !lower || !upper || !kp || !kd || !effort_limit || !out_torque)
+        return fail(JM_EINVAL, "jm_block_pd_controller: null argument");
+    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_pd_controller: bad sizes");
+    if (control_dt < 0.0) return fail(JM_EINVAL, "Integration backward in time is not supported.");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_pd_controller: bad dtype");
+    jm::PdParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.M = M;
+    p.dt = control_dt;
+    for (int m = 0; m < M; ++m)
+    {
+        p.enc_index[m] = encoder_index[m];
+        for (int k = 0; k < 3; ++k) { p.lo[k][m] = lower[k * M + m]; p.hi[k][m] = upper[k * M + m]; }
+        p.kp[m] = kp[m]; p.kd[m] = kd[m]; p.effort_limit[m] = effort_limit[m];
+    }
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_pd_controller<T>), grid, dim3(256), 0, s, p, (const T *)encoder,
+                           (T *)command_state, (T *)out_torque, (long long)B);
+    });
+}
+
+int32_t jm_block_mahony_filter(int32_t dtype, int64_t B, int32_t n_imu, const void * imu, void * quat, void * omega,
+                               void * cf, void * bias, double kp, double ki, double dt, void * stream)
+{
+    if (!imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_filter: null argument");
+    if (B <= 0 || n_imu <= 0) return fail(JM_EINVAL, "jm_block_mahony_filter: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_filter: bad dtype");
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_mahony<T>), grid, dim3(256), 0, s, n_imu, (const T *)imu, (T *)quat,
+                           (T *)omega, (T *)cf, (T *)bias, kp, ki, dt, (long long)B);
+    });
+}
+
+int32_t jm_block_pd_adapter(int32_t dtype, int64_t B, int32_t M, const void * action, int32_t order, void * command_state,
+                            const double * lower, const double * upper, int32_t is_instantaneous, const double * velocity_deadband,
+                            double step_dt, void * out, void * stream)
+{
+    if (!action || !command_state || !lower || !upper || !out) return fail(JM_EINVAL, "jm_block_pd_adapter: null argument");
+    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_pd_adapter: bad sizes");
+    if (order != 0 && order != 1) return fail(JM_EINVAL, "Derivative order of the target must be either 0 or 1.");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_pd_adapter: bad dtype");
+    jm::PdAdapterParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.M = M; p.order = order; p.instantaneous = is_instantaneous != 0; p.dt = step_dt;
+    for (int m = 0; m < M; ++m)
+    {
+        for (int k = 0; k < 3; ++k) { p.lo[k][m] = lower[k * M + m]; p.hi[k][m] = upper[k * M + m]; }
+        p.deadband[m] = velocity_deadband ? velocity_deadband[m] : -1.0;
+    }
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_pd_adapter<T>), grid, dim3(256), 0, s, p, (const T *)action, (T *)command_state,
+                           (T *)out, (long long)B);
+    });
+}
+
+int32_t jm_block_motor_safety_limit(int32_t dtype, int64_t B, int32_t M, const void * encoder, const int32_t * encoder_index,
+                                    const void * command, const double * kp, const double * kd, const double * soft_lo,
+                                    const double * soft_hi, const double * vel_lim, const double * eff_lim, void * out, void * stream)
+{
+    if (!encoder || !encoder_index || !command || !kp || !kd || !soft_lo || !soft_hi || !vel_lim || !eff_lim || !out)
+        return fail(JM_EINVAL, "jm_block_motor_safety_limit: null argument");
+    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_motor_safety_limit: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_motor_safety_limit: bad dtype");
+    jm::SafetyParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.M = M;
+    for (int m = 0; m < M; ++m)
+    {
+        p.enc_index[m] = encoder_index[m];
+        p.kp[m] = kp[m]; p.kd[m] = kd[m]; p.soft_lo[m] = soft_lo[m]; p.soft_hi[m] = soft_hi[m];
+        p.vel_lim[m] = vel_lim[m]; p.eff_lim[m] = eff_lim[m];
+    }
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_motor_safety_limit<T>), grid, dim3(256), 0, s, p, (const T *)encoder,
+                           (const T *)command, (T *)out, (long long)B);
+    });
+}
+
+int32_t jm_deform_plan_create(const jm_deform_desc * desc, jm_deform_plan ** out)
+{
+    const int32_t rc = plan_create("jm_deform_plan_create", desc, out, jm::deform_pack);
+    if (rc != JM_OK) return rc;
+    (*out)->n_imu = desc->n_imu; (*out)->n_flex = desc->n_flex; (*out)->ignore_twist = desc->ignore_twist != 0;
+    return JM_OK;
+}
+
+int32_t jm_deform_plan_destroy(jm_deform_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_deformation_estimator(const jm_deform_plan * p, int32_t dtype, int64_t B, const void * encoder,
+                                       const void * imu_quat, void * out_quat, void * out_rpy, void * stream)
+{
+    if (!p || !encoder || !imu_quat || !out_quat) return fail(JM_EINVAL, "jm_block_deformation_estimator: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad dtype");
+    const jm::DeformArgs a{p->dev.it, p->dev.dt, p->n_imu, p->n_flex, p->ignore_twist};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_deformation_estimator<T>), grid, dim3(256), 0, s, a, (const T *)encoder,
+                           (const T *)imu_quat, (T *)out_quat, (T *)out_rpy, (long long)B);
+    });
+}
+
+int32_t jm_attitude_plan_create(const jm_attitude_desc * desc, jm_attitude_plan ** out)
+{
+    const int32_t rc = plan_create("jm_attitude_plan_create", desc, out, jm::attitude_pack);
+    if (rc != JM_OK) return rc;
+    (*out)->n_imu = desc->n_imu;
+    return JM_OK;
+}
+
+int32_t jm_attitude_plan_destroy(jm_attitude_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_attitude_init(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * q, const void * imu,
+                               const uint8_t * lane_mask, int32_t exact_init, void * quat, void * omega, void * cf, void * bias,
+                               void * twist, void * rpy, void * stream)
+{
+    if (!p || !q || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_attitude_init: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_attitude_init: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_attitude_init: bad dtype");
+    const jm::AttitudeArgs a{p->dev.it, p->dev.dt, p->n_imu};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_attitude_init<T>), grid, dim3(256), 0, s, a, (int)(exact_init != 0), (const T *)q,
+                           (const T *)imu, lane_mask, (T *)quat, (T *)omega, (T *)cf, (T *)bias,
+                           (T *)twist, (T *)rpy, (long long)B);
+    });
+}
+
+int32_t jm_block_mahony_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu, void * quat, void * omega,
+                                 void * cf, void * bias, double dt, int32_t ignore_twist, void * rpy, void * stream)
+{
+    if (!p || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_observer: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_mahony_observer: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_observer: bad dtype");
+    const jm::AttitudeArgs a{p->dev.it, p->dev.dt, p->n_imu};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_mahony_observer<T>), grid, dim3(256), 0, s, a, (const T *)imu, (T *)quat,
+                           (T *)omega, (T *)cf, (T *)bias, dt, (int)(ignore_twist != 0), (T *)rpy, (long long)B);
+    });
+}
+
+int32_t jm_block_body_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu_quat, const void * imu_omega,
+                               void * quat, void * omega, void * twist, int32_t twist_mode, double time_constant_inv, double dt,
+                               void * rpy, void * stream)
+{
+    if (!p || !imu_quat || !imu_omega || !quat || !omega) return fail(JM_EINVAL, "jm_block_body_observer: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_body_observer: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_body_observer: bad dtype");
+    if (twist_mode < 0 || twist_mode > 2) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode must be 0, 1 or 2");
+    if (twist_mode == 2 && !twist) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode 2 needs the twist state");
+    if (quat == imu_quat) return fail(JM_EINVAL, "jm_block_body_observer: quat must not alias imu_quat");
+    const jm::AttitudeArgs a{p->dev.it, p->dev.dt, p->n_imu};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_body_observer<T>), grid, dim3(256), 0, s, a, (const T *)imu_quat,
+                           (const T *)imu_omega, (T *)quat, (T *)omega, (T *)twist, (int)twist_mode,
+                           time_constant_inv, dt, (T *)rpy, (long long)B);
+    });
+}
+
+// ziggurat tables: computed once on the host (random.cc:66-96), one copy per device
+static int32_t ziggurat_tables_on_device(jm::rnd::ZigguratTables ** out)
+{
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    static std::mutex mtx;
+    static std::map<int, jm::rnd::ZigguratTables *> tables;
+    std::lock_guard<std::mutex> lock(mtx);
+    auto it = tables.find(dev);
+    if (it == tables.end())
+    {
+        jm::rnd::ZigguratTables host;
+        jm::rnd::ziggurat_tables(host);
+        jm::rnd::ZigguratTables * tab = nullptr;
+        HIP_TRY(hipMalloc((void **)&tab, sizeof(host)));
+        HIP_TRY(hipMemcpy(tab, &host, sizeof(host), hipMemcpyHostToDevice));
+        tables[dev] = tab;
+        *out = tab;
+    }
+    else *out = it->second;
+    return JM_OK;
+}
+
+int32_t jm_block_sensor_noise(int32_t dtype, int64_t B, int32_t n_sensors, int32_t n_fields, void * data,
+                              uint64_t * rng_state, const double * noise_std, const double * bias,
+                              const double * rot_bias_inv, void * stream)
+{
+    if (!data) return fail(JM_EINVAL, "jm_block_sensor_noise: null data");
+    if (B <= 0 || n_sensors <= 0 || n_fields <= 0 || n_fields > JM_NOISE_MAX_FIELDS ||
+        n_sensors * n_fields > JM_NOISE_MAX_ROWS)
+        return fail(JM_EINVAL, "jm_block_sensor_noise: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_sensor_noise: bad dtype");
+    if (noise_std && !rng_state) return fail(JM_EINVAL, "jm_block_sensor_noise: noise needs the generator states");
+    if (rot_bias_inv && (n_fields != 6 || n_sensors > JM_NOISE_MAX_ROT || !bias))
+        return fail(JM_EINVAL, "jm_block_sensor_noise: the rotation bias applies to IMU fields (6 rows) with a bias");
+    if (!noise_std && !bias) return JM_OK;
+    jm::NoiseParams p{};
+    p.n_sensors = n_sensors; p.n_fields = n_fields;
+    p.has_noise = noise_std != nullptr; p.has_bias = bias != nullptr; p.has_rot = rot_bias_inv != nullptr;
+    for (int i = 0; i < n_sensors * n_fields; ++i)
+    {
+        if (noise_std)
+        {
+            if (!(noise_std[i] >= 0.0)) return fail(JM_EINVAL, "jm_block_sensor_noise: negative noise standard deviation");
+            p.noise_std[i] = (float)noise_std[i];
+        }
+        if (bias) p.bias[i] = bias[i];
+    }
+    if (rot_bias_inv)
+        for (int s = 0; s < n_sensors; ++s)
+            for (int k = 0; k < 9; ++k) p.rot[s][k] = rot_bias_inv[9 * s + k];
+    jm::rnd::ZigguratTables * tab = nullptr;
+    {
+        const int32_t rc = ziggurat_tables_on_device(&tab);
+        if (rc != JM_OK) return rc;
+    }
+    return launch_lanes(dtype, B, (unsigned)n_sensors, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_sensor_noise<T>), grid, dim3(256), 0, s, p, tab, (T *)data, rng_state, (long long)B);
+    });
+}
+
+int32_t jm_block_sensor_delay(int32_t dtype, int64_t B, int32_t n_sensors, int32_t n_fields, void * data,
+                              const void * history, const int32_t * slot, const double * times, int32_t n_history,
+                              uint64_t * rng_state, const double * delay, const double * jitter, int32_t order,
+                              void * stream)
+{
+    if (!data) return fail(JM_EINVAL, "jm_block_sensor_delay: null data");
+    if (B <= 0 || n_sensors <= 0 || n_fields <= 0 || n_fields > JM_NOISE_MAX_FIELDS || n_sensors > JM_NOISE_MAX_ROWS)
+        return fail(JM_EINVAL, "jm_block_sensor_delay: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_sensor_delay: bad dtype");
+    if (order != 0 && order != 1)
+        return fail(JM_ENOTIMPL, "`delayInterpolationOrder` must be either 0 or 1.");  // abstract_sensor.hxx:399-403
+    if (history && (!slot || !times || n_history < 1 || n_history > JM_DELAY_MAX_HISTORY))
+        return fail(JM_EINVAL, "jm_block_sensor_delay: the history needs 1..64 samples with their slots and times");
+    if (!history && !rng_state) return JM_OK;
+    jm::DelayParams p{};
+    p.n_sensors = n_sensors; p.n_fields = n_fields; p.order = order;
+    p.has_history = history != nullptr; p.n_hist = history ? n_history : 0;
+    for (int i = 0; i < p.n_hist; ++i)
+    {
+        if (i > 0 && !(times[i] >= times[i - 1])) return fail(JM_EINVAL, "jm_block_sensor_delay: sample times must ascend");
+        p.slot[i] = slot[i];
+        p.times[i] = times[i];
+    }
+    for (int s = 0; s < n_sensors; ++s)
+    {
+        p.delay[s] = delay ? delay[s] : 0.0;
+        p.jitter[s] = jitter ? (float)jitter[s] : 0.0f;
+        if (!(p.delay[s] >= 0.0) || !(p.jitter[s] >= 0.0f)) return fail(JM_EINVAL, "jm_block_sensor_delay: negative delay or jitter");
+    }
+    return launch_lanes(dtype, B, (unsigned)n_sensors, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_sensor_delay<T>), grid, dim3(256), 0, s, p, (T *)data, (const T *)history, rng_state, (long long)B);
+    });
+}
+
+int32_t jm_block_model_bias(int32_t dtype, int64_t B, int32_t njoints, int32_t first_joint, const double * nominal,
+                            const float * std4, uint64_t * rng_state, const uint8_t * mask, void * model_lane, void * stream)
+{
+    if (!nominal || !std4 || !rng_state || !model_lane) return fail(JM_EINVAL, "jm_block_model_bias: null argument");
+    if (B <= 0 || njoints < 1 || first_joint < 1 || first_joint > njoints) return fail(JM_EINVAL, "jm_block_model_bias: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_model_bias: bad dtype");
+    for (int i = 0; i < 4; ++i)
+        if (!(std4[i] >= 0.0f)) return fail(JM_EINVAL, "jm_block_model_bias: negative standard deviation");
+    jm::BiasParams p{};
+    p.njoints = njoints; p.first = first_joint;
+    p.inertia_std = std4[0]; p.mass_std = std4[1]; p.com_std = std4[2]; p.pos_std = std4[3];
+    jm::rnd::ZigguratTables * tab = nullptr;
+    const int32_t rc = ziggurat_tables_on_device(&tab);
+    if (rc != JM_OK) return rc;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_model_bias<T>), grid, dim3(256), 0, s, p, tab, nominal, rng_state, mask, (T *)model_lane, (long long)B);
+    });
+}
+
+int32_t jm_engine_rng_seed(const uint32_t * seed, int64_t B, uint64_t * state_out)
+{
+    if (!seed || !state_out || B <= 0) return fail(JM_EINVAL, "jm_engine_rng_seed: bad arguments");
+    for (int64_t lane = 0; lane < B; ++lane)
+    {
+        // internal::generateState (random.hxx:20-44): two 32-bit words of the sequence, low word first
+        std::seed_seq seq{seed[lane]};
+        uint32_t w[2];
+        seq.generate(w, w + 2);
+        state_out[lane] = jm::rnd::pcg32_init((uint64_t)w[0] | ((uint64_t)w[1] << 32));
+    }
+    return JM_OK;
+}
+
+int32_t jm_sensor_rng_seed(const uint32_t * group_seed, int64_t B, int32_t n_sensors, uint64_t * state_out)
+{
+    if (!group_seed || !state_out || B <= 0 || n_sensors <= 0) return fail(JM_EINVAL, "jm_sensor_rng_seed: bad arguments");
+    std::vector<uint32_t> words((size_t)n_sensors);
+    for (int64_t lane = 0; lane < B; ++lane)
+    {
+        std::seed_seq seq{group_seed[lane]};
+        seq.generate(words.begin(), words.end());
+        for (int32_t s = 0; s < n_sensors; ++s) state_out[(size_t)s * B + lane] = jm::rnd::pcg32_init(words[s]);
+    }
+    return JM_OK;
+}
+}  // extern "C"

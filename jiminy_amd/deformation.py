@@ -24,13 +24,11 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .model import (BACKLASH_JOINT_SUFFIX, FLEXIBLE_JOINT_SUFFIX, JT_FREEFLYER, JT_RU, JT_RUBU, JT_RUBX, JT_RUBY, JT_RUBZ, JT_RX,
-                    JT_RY, JT_RZ, JT_SPHERICAL, CompiledModel)
+from ._plan import AXIS_KIND, SEG_AXIS, SEG_NONE, SEG_X, SEG_Y, SEG_Z, SegmentTable, fill_desc  # noqa: F401 (kinds of jm_deform_desc)
+from .model import (BACKLASH_JOINT_SUFFIX, FLEXIBLE_JOINT_SUFFIX, JT_FREEFLYER, JT_RUBU, JT_RUBX, JT_RUBY, JT_RUBZ, JT_SPHERICAL,
+                    CompiledModel)
 
 Chain = Tuple[List[str], List[Optional[str]], List[bool]]
-
-# joint kinds of a plan segment (include/jiminy_hip.h, jm_deform_desc)
-SEG_NONE, SEG_X, SEG_Y, SEG_Z, SEG_AXIS = 0, 1, 2, 3, 4
 
 
 def flexibility_imu_frame_chains(parents: Sequence[int], root_is_free: bool, flex_joint_of: Dict[str, int],
@@ -167,22 +165,15 @@ class DeformationPlan:
 def make_desc(*, n_imu: int, n_enc: int, ignore_twist: bool, chain_nflex, chain_orphan, chain_imu, chain_imu_frame, flex_frame,
               flex_flipped, frame_seg_start, seg_kind, seg_enc, seg_rot, seg_axis, seg_ratio) -> Tuple["_abi.DeformDesc", List[np.ndarray]]:
     """`jm_deform_desc` from plain arrays (layout: include/jiminy_hip.h); the second value keeps them alive."""
-    import ctypes as C
-    i32 = lambda x: np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)      # noqa: E731
-    f64 = lambda x: np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.float64)    # noqa: E731
-    ints = {k: i32(v) for k, v in dict(chain_nflex=chain_nflex, chain_orphan=chain_orphan, chain_imu=chain_imu,
-                                       chain_imu_frame=chain_imu_frame, flex_frame=flex_frame, flex_flipped=flex_flipped,
-                                       frame_seg_start=frame_seg_start, seg_kind=seg_kind, seg_enc=seg_enc).items()}
-    dbls = {k: f64(v) for k, v in dict(seg_rot=seg_rot, seg_axis=seg_axis, seg_ratio=seg_ratio).items()}
     d = _abi.DeformDesc()
+    a, keep = fill_desc(d, dict(chain_nflex=chain_nflex, chain_orphan=chain_orphan, chain_imu=chain_imu,
+                                chain_imu_frame=chain_imu_frame, flex_frame=flex_frame, flex_flipped=flex_flipped,
+                                frame_seg_start=frame_seg_start, seg_kind=seg_kind, seg_enc=seg_enc),
+                        dict(seg_rot=seg_rot, seg_axis=seg_axis, seg_ratio=seg_ratio))
     d.n_imu, d.n_enc, d.ignore_twist = int(n_imu), int(n_enc), int(bool(ignore_twist))
-    d.n_chain, d.n_flex = len(ints["chain_nflex"]), len(ints["flex_frame"])
-    d.n_frame, d.n_seg = len(ints["frame_seg_start"]) - 1, len(ints["seg_kind"])
-    for k, a in ints.items():
-        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_int32)))
-    for k, a in dbls.items():
-        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_double)))
-    return d, list(ints.values()) + list(dbls.values())
+    d.n_chain, d.n_flex = len(a["chain_nflex"]), len(a["flex_frame"])
+    d.n_frame, d.n_seg = len(a["frame_seg_start"]) - 1, len(a["seg_kind"])
+    return d, keep
 
 
 def build_plan(model: CompiledModel, imu_frame_names: Sequence[str], flex_frame_names: Sequence[str],
@@ -216,42 +207,16 @@ def build_plan(model: CompiledModel, imu_frame_names: Sequence[str], flex_frame_
     imu_sensor_of = {s["frame"]: i for i, s in enumerate(model.sensors.get("ImuSensor", []))}
 
     # frames of the theoretical model, as segment lists
-    seg_kind: List[int] = []
-    seg_enc: List[int] = []
-    seg_rot: List[np.ndarray] = []
-    seg_axis: List[np.ndarray] = []
-    seg_ratio: List[float] = []
-    frame_seg_start = [0]
+    segs = SegmentTable()
 
-    def add_frame(joint: int, R_frame: np.ndarray) -> int:
-        """Frame rigidly attached to `joint` with rotation `R_frame`; returns its index in the plan."""
-        path, j = [], joint
-        while j != 0:
-            path.append(j)
-            j = int(model.parents[j])
-        const = np.eye(3)
-        for j in reversed(path):
-            const = const @ model.placement_R[j]
-            t = int(model.jtypes[j])
-            if t in (JT_RX, JT_RY, JT_RZ, JT_RU) and not _is_backlash(model, j):
-                if j not in encoder_of:
-                    raise ValueError("The robot must have one encoder per mechanical joints.")
-                seg_kind.append({JT_RX: SEG_X, JT_RY: SEG_Y, JT_RZ: SEG_Z, JT_RU: SEG_AXIS}[t])
-                seg_enc.append(encoder_of[j][0])
-                seg_ratio.append(encoder_of[j][1])
-                seg_rot.append(const)
-                seg_axis.append(np.asarray(model.axes[j], dtype=np.float64))
-                const = np.eye(3)
-            # (prismatic joints do not rotate; spherical, backlash and free-flyer joints sit at the identity)
-        const = const @ R_frame
-        if len(seg_kind) == frame_seg_start[-1] or not np.array_equal(const, np.eye(3)):
-            seg_kind.append(SEG_NONE)
-            seg_enc.append(-1)
-            seg_ratio.append(0.0)
-            seg_rot.append(const)
-            seg_axis.append(np.zeros(3))
-        frame_seg_start.append(len(seg_kind))
-        return len(frame_seg_start) - 2
+    def joint_segment(j: int):
+        # (prismatic joints do not rotate; spherical, backlash and free-flyer joints sit at the identity)
+        t = int(model.jtypes[j])
+        if t not in AXIS_KIND or _is_backlash(model, j):
+            return None
+        if j not in encoder_of:
+            raise ValueError("The robot must have one encoder per mechanical joints.")
+        return AXIS_KIND[t], encoder_of[j][0], model.axes[j], encoder_of[j][1]
 
     chain_nflex, chain_orphan, chain_imu, chain_imu_frame, flex_frame, flex_flipped = [], [], [], [], [], []
     imu_indices, parent_names, orphans = [], [], []
@@ -270,7 +235,7 @@ def build_plan(model: CompiledModel, imu_frame_names: Sequence[str], flex_frame_
             indices.append(imu_sensor_of[name])
             fr = model.frame(name)
             chain_imu.append(imu_sensor_of[name])
-            chain_imu_frame.append(add_frame(int(fr.parent_joint), fr.R))
+            chain_imu_frame.append(segs.add_frame(model, int(fr.parent_joint), fr.R, joint_segment))
         imu_indices.append(tuple(indices))
         for name, flip in zip(flexs, flipped):
             # nearest ancestor joint that belongs to the theoretical model and is not a flexibility (:776-788)
@@ -278,13 +243,13 @@ def build_plan(model: CompiledModel, imu_frame_names: Sequence[str], flex_frame_
             while j != 0 and (int(model.jtypes[j]) == JT_SPHERICAL or _is_backlash(model, j)):
                 j = int(model.parents[j])
             parent_names.append(model.joint_names[j])
-            flex_frame.append(add_frame(j, np.eye(3)))
+            flex_frame.append(segs.add_frame(model, j, np.eye(3), joint_segment))
             flex_flipped.append(int(flip))
 
     arrays = dict(n_imu=len(model.sensors.get("ImuSensor", [])), n_enc=len(encoders), ignore_twist=bool(ignore_twist),
                   chain_nflex=chain_nflex, chain_orphan=chain_orphan, chain_imu=chain_imu, chain_imu_frame=chain_imu_frame,
-                  flex_frame=flex_frame, flex_flipped=flex_flipped, frame_seg_start=frame_seg_start, seg_kind=seg_kind,
-                  seg_enc=seg_enc, seg_rot=np.array(seg_rot), seg_axis=np.array(seg_axis), seg_ratio=seg_ratio)
+                  flex_frame=flex_frame, flex_flipped=flex_flipped, frame_seg_start=segs.frame_seg_start, seg_kind=segs.kind,
+                  seg_enc=segs.index, seg_rot=np.array(segs.rot), seg_axis=np.array(segs.axis), seg_ratio=segs.ratio)
     return DeformationPlan(chains=chains, flexibility_frame_names=[n for flexs, _, _ in chains for n in flexs],
                            is_chain_orphan=orphans, imu_indices=imu_indices, parent_flex_joint_names=parent_names,
                            ignore_twist=bool(ignore_twist), compute_rpy=bool(compute_rpy), arrays=arrays)

@@ -1,6 +1,7 @@
 // Host emulation of the attitude observers (tests only): the per-lane bodies of jiminy_amd/csrc/jm_attitude.h
-// (`attitude_init_lane`, `mahony_observer_lane`, `body_observer_lane`: what the three kernels run) and the description
-// check / packing of `jm_attitude_plan_create`, compiled by the host compiler and run lane after lane.
+// (`attitude_init_lane`, `mahony_observer_lane`, `body_observer_lane`, `mahony_lane` with one pair of gains: what the four
+// kernels run) and the description check / packing of `jm_attitude_plan_create`, compiled by the host compiler and run lane
+// after lane.
 #define JM_HOST_EMU 1
 #include <cstring>
 
@@ -76,6 +77,23 @@ extern "C" int emu_body_observer(const jm_attitude_desc * desc, int dtype, long 
         else
             jm::body_observer_lane<float>(dt.data(), desc->n_imu, (const float *)imu_quat, (const float *)imu_omega, (float *)quat,
                                           (float *)omega, (float *)twist, twist_mode, time_constant_inv, step, (float *)rpy, B, lane);
+    }
+    return JM_OK;
+}
+
+// the plain `mahony_filter` function (`k_mahony`: one pair of gains for every IMU, no plan)
+extern "C" int emu_mahony_filter(int dtype, long long B, int n_imu, const void * imu, void * quat, void * omega, void * cf, void * bias,
+                                 double kp, double ki, double step)
+{
+    if (!imu || !quat || !omega || !cf || !bias || B <= 0 || n_imu <= 0 || (dtype != JM_F64 && dtype != JM_F32)) return JM_EINVAL;
+    for (long long lane = 0; lane < B; ++lane)
+    {
+        if (dtype == JM_F64)
+            jm::mahony_lane<jm::TILT_FUSED>(n_imu, jm::UniformGains<double>{kp, ki}, (const double *)imu, (double *)quat, (double *)omega,
+                                            (double *)cf, (double *)bias, step, B, lane);
+        else
+            jm::mahony_lane<jm::TILT_FUSED>(n_imu, jm::UniformGains<float>{(float)kp, (float)ki}, (const float *)imu, (float *)quat,
+                                            (float *)omega, (float *)cf, (float *)bias, (float)step, B, lane);
     }
     return JM_OK;
 }

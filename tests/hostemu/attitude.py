@@ -1,4 +1,5 @@
-"""Build + ctypes driver of attitude.cpp: the three attitude-observer kernel bodies on the host (tests only)."""
+"""Build + ctypes driver of attitude.cpp: the attitude-observer kernel bodies and the plain Mahony function on the host
+(tests only)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +22,7 @@ def _lib() -> C.CDLL:
         return _LIB
     os.makedirs(codegen.BUILD, exist_ok=True)
     out = os.path.join(codegen.BUILD, "libemu_attitude.so")
-    deps = [os.path.join(_HERE, "attitude.cpp"), os.path.join(codegen.CSRC, "jm_attitude.h"), os.path.join(codegen.CSRC, "jm_deform.h"),
+    deps = [os.path.join(_HERE, "attitude.cpp"), os.path.join(codegen.CSRC, "jm_attitude.h"), os.path.join(codegen.CSRC, "jm_rotation.h"),
             os.path.join(codegen.CSRC, "jm_math.h"), os.path.join(codegen.CSRC, "..", "..", "include", "jiminy_hip.h")]
     if (not os.path.exists(out)) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         subprocess.check_call(emu.host_compiler() + [os.path.join(_HERE, "attitude.cpp"), "-o", out])
@@ -31,6 +32,7 @@ def _lib() -> C.CDLL:
     L.emu_mahony_observer.argtypes = [desc, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp, C.c_char_p, C.c_size_t]
     L.emu_body_observer.argtypes = [desc, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, C.c_int, C.c_double, C.c_double, vp,
                                     C.c_char_p, C.c_size_t]
+    L.emu_mahony_filter.argtypes = [C.c_int, C.c_longlong, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double]
     _LIB = L
     return L
 
@@ -81,3 +83,15 @@ def body(desc, imu_quat, imu_omega, quat, omega, twist, twist_mode: int, time_co
     rc = _lib().emu_body_observer(C.byref(desc), _code(dtype), B, _ptr(iq), _ptr(io), _ptr(quat), _ptr(omega), _ptr(twist),
                                   int(twist_mode), float(time_constant_inv), float(dt), _ptr(rpy), err, 512)
     _raise(rc, err, "emu_body_observer")
+
+
+def mahony_function(imu, quat, omega, cf, bias, kp: float, ki: float, dt: float) -> None:
+    """`mahony_lane` with one pair of gains (what `k_mahony` runs); quat, omega, cf, bias are updated in place."""
+    dtype = quat.dtype
+    imu = np.ascontiguousarray(imu, dtype=dtype)
+    n_imu, B = quat.shape[1:]
+    assert imu.shape == (n_imu, 6, B) and quat.shape == (4, n_imu, B) and omega.shape == cf.shape == bias.shape == (3, n_imu, B)
+    rc = _lib().emu_mahony_filter(_code(dtype), B, n_imu, _ptr(imu), _ptr(quat), _ptr(omega), _ptr(cf), _ptr(bias), float(kp),
+                                  float(ki), float(dt))
+    if rc != 0:
+        raise ValueError(f"emu_mahony_filter failed with code {rc}")

@@ -21,8 +21,8 @@ def _lib() -> C.CDLL:
         return _LIB
     os.makedirs(codegen.BUILD, exist_ok=True)
     out = os.path.join(codegen.BUILD, "libemu_deform.so")
-    deps = [os.path.join(_HERE, "deform.cpp"), os.path.join(codegen.CSRC, "jm_deform.h"), os.path.join(codegen.CSRC, "jm_math.h"),
-            os.path.join(codegen.CSRC, "..", "..", "include", "jiminy_hip.h")]
+    deps = [os.path.join(_HERE, "deform.cpp"), os.path.join(codegen.CSRC, "jm_deform.h"), os.path.join(codegen.CSRC, "jm_rotation.h"),
+            os.path.join(codegen.CSRC, "jm_math.h"), os.path.join(codegen.CSRC, "..", "..", "include", "jiminy_hip.h")]
     if (not os.path.exists(out)) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         subprocess.check_call(emu.host_compiler() + [os.path.join(_HERE, "deform.cpp"), "-o", out])
     L = C.CDLL(out)

@@ -11,7 +11,7 @@ Tolerances.
 * `mahony.n3_singular` puts one IMU of every second lane upside down on its first tick (tilt within 5e-6 of -e_z, the
   singular branch of `swing_from_vector`); its bound is max(1e-13, 4 x the deviation the numpy float64 restatement shows
   on the same case).  That tick is authored at rest, so the filter's early return hands the stored quaternion to the twist
-  removal bit for bit, and the tilt is evaluated without fused multiply-adds in the kernel (`attitude_tilt`): the one
+  removal bit for bit, and the tilt is evaluated without fused multiply-adds in the kernel (`quat_tilt<TILT_ROUNDED>`): the one
   quantity that the branch amplifies by 1e5 is then the same number in all three implementations.  Measured (quat | rpy):
   numpy restatement 0 | 0 (the same operations in the same order as the reference's), emulated kernel 7.8e-16 | 7.5e-15,
   MI355X 2.2e-15 | 9.1e-15; the bound is its floor, 1e-13.  Regular cases: emulated kernel 0 | 4.4e-16, MI355X 3.3e-16 |

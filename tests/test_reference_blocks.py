@@ -9,6 +9,7 @@ the fixture's inputs:
 
   * oracle/blocks_numpy.py (the scalar restatement the other tests use as their checker)      -- CPU
   * the tensor programs of jiminy_amd/blocks.py                                              -- CPU
+  * the per-lane body of `k_mahony` (jm_attitude.h `mahony_lane`) compiled for the host, tests/hostemu   -- CPU
   * the `jm_block_*` HIP kernels behind include/jiminy_hip.h, through `HipBlocks`            -- GPU
 
 Tolerances: 1e-13 relative to the largest magnitude of the compared array (the reference compiles with
@@ -97,6 +98,24 @@ def test_tensor_program_blocks_reproduce_the_reference(ref):
         for got, key in ((q, "mh_q_out"), (bias, "mh_bias_out"), (om, "mh_omega"), (cf, "mh_cf")):
             assert close(got.numpy(), ref[key][t])
     assert close(torch.stack(blocks.compute_tilt_from_quat(tt(ref["tilt_q"]))).numpy(), ref["tilt_v"])
+
+
+# ------------------------------------------------------------------ the kernel body of the Mahony function on the host
+@pytest.mark.parametrize("B", [1, 65])
+def test_host_emulated_mahony_function_reproduces_the_reference(ref, B):
+    """`mahony_lane` as `k_mahony` instantiates it, float64, B lanes at a time (65: one past a wave): every lane of the
+    fixture alone, or its first and last 65 lanes."""
+    from tests.hostemu import attitude as emu
+    n = ref["mh_imu"].shape[-1]
+    for lanes in ([slice(b, b + 1) for b in range(n)] if B == 1 else [slice(0, B), slice(n - B, n)]):
+        for t in range(ref["mh_imu"].shape[0]):
+            q, bias = np.ascontiguousarray(ref["mh_q_in"][t][..., lanes]), np.ascontiguousarray(ref["mh_bias_in"][t][..., lanes])
+            assert q.shape == (4, 1, B)
+            om, cf = np.zeros_like(bias), np.zeros_like(bias)
+            emu.mahony_function(ref["mh_imu"][t][None, :, lanes], q, om, cf, bias, float(ref["mh_kp"]), float(ref["mh_ki"]),
+                                float(ref["mh_dt"]))
+            for got, key in ((q, "mh_q_out"), (bias, "mh_bias_out"), (om, "mh_omega"), (cf, "mh_cf")):
+                assert close(got, ref[key][t][..., lanes])
 
 
 # ------------------------------------------------------------------ the HIP kernels, through the C ABI

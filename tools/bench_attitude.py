@@ -3,7 +3,7 @@
 flexible arm (tests/data/flex_arm.urdf, 4 IMUs).
     python tools/bench_attitude.py [--envs 65536] [--calls 50] [--reps 5] [--steps 20]
 * kernels, `--calls` back-to-back launches each between two device events, `--reps` repetitions (median, min, max in
-  microseconds per launch): `jm_block_mahony_filter` (`k_mahony`, unchanged by these blocks: the yardstick),
+  microseconds per launch): `jm_block_mahony_filter` (`k_mahony`, the plain function around the same `mahony_lane`: the yardstick),
   `jm_block_mahony_observer` with every option off and with twist removal + Euler angles, `jm_block_body_observer`
   (twist integrated, Euler angles), `jm_block_attitude_init` (exact);
 * environment: ms per step of the ANYmal `PDControlledWalkerVecEnv` with and without the two blocks, `--reps` repetitions of

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Development build of a topology library that KEEPS its object files, so that only the translation units named on the
 command line are recompiled:
-    python tools/dev_parts.py <model> <tag> [main] [1..9] [-- extra hipcc flags]
+    python tools/dev_parts.py <model> <tag> [main] [blocks] [1..16] [-- extra hipcc flags]
         ->  jiminy_amd/csrc/build/libjm_<hash>_<tag>.so   (objects under jiminy_amd/csrc/build/dev_<hash>_<tag>/)
 Parts that have no object yet are compiled too.  Select the library at run time with JIMINY_AMD_LIB_TAG=<tag>."""
 import os
@@ -39,9 +39,12 @@ def main():
     os.makedirs(objdir, exist_ok=True)
     common = [f"--offload-arch={codegen.OFFLOAD_ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
               f"-DJM_TOPO_HEADER=\"{hdr}\"", "-Wno-unused-value", "-ffp-contract=fast"] + list(codegen.BUILD_VARIANTS[v]) + extra
-    parts = ([1, 2, 3, 4, 5, 6] if codegen.quad_structure(model) is not None else [1]) + ([7, 8, 9, 10] if codegen.qcon_split(model) else [])
+    # (the part list of codegen.build_library)
+    parts = ([1, 2, 3, 4, 5, 6, 11, 12] if codegen.quad_structure(model) is not None else [1, 15, 16]) + \
+            ([7, 8, 9, 10, 13, 14] if codegen.qcon_split(model) else [])
     pf = codegen.part_flags(model)
-    units = {"main": [codegen.HIPCC] + common + ["-DJM_SPLIT_CONSTRAINT", "-c", os.path.join(codegen.CSRC, "jm_lib.cpp")]}
+    units = {"main": [codegen.HIPCC] + common + ["-DJM_SPLIT_CONSTRAINT", "-c", os.path.join(codegen.CSRC, "jm_lib.cpp")],
+             "blocks": [codegen.HIPCC] + common + ["-c", os.path.join(codegen.CSRC, "jm_lib_blocks.cpp")]}
     for p in parts:
         units[str(p)] = [codegen.HIPCC] + common + pf.get(str(p), []) + [f"-DJM_CON_PART={p}", "-c",
                                                                         os.path.join(codegen.CSRC, "jm_lib_constraint.cpp")]
