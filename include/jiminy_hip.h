@@ -616,6 +616,63 @@ int32_t jm_block_body_observer(const jm_attitude_plan * plan, int32_t dtype, int
                                const void * imu_omega, void * quat, void * omega, void * twist, int32_t twist_mode,
                                double time_constant_inv, double dt, void * rpy, void * stream);
 
+/* ---- Frame kinematics: pose and velocity of named frames from `q`, `v` (what the reference reads from `pinocchio_data.oMf`
+ * and `getFrameVelocity`), and the SE3 step average of its quantity layer; batched, one lane = one environment.  New symbols
+ * only: no existing structure or signature changed with them.
+ * jm_frames_desc: the plan (host arrays, copied by jm_frames_plan_create).  Per frame a reference frame `frame_mode` (0 LOCAL,
+ *   1 LOCAL_WORLD_ALIGNED, 2 ODOMETRY: the step average only, the velocity of such a frame is LOCAL) and the walk from the
+ *   universe to the frame as a list of segments `frame_seg_start[f] .. frame_seg_start[f + 1] - 1`, at most 256 per frame: a
+ *   segment is a constant placement (`seg_rot` row-major 3x3, `seg_trans`) followed by the motion of joint `seg_joint` read
+ *   from `q` `[nq][B]` at `seg_q_index` and `v` `[nv][B]` at `seg_v_index`: `seg_kind` 0 none (the frame's own placement),
+ *   1 / 2 / 3 revolute about x / y / z, 4 revolute about the unit vector `seg_axis`, 5 unbounded revolute about `seg_axis`
+ *   with `(cos, sin) = q[i], q[i + 1]`, 6 spherical (unit quaternion `q[i .. i + 3]` xyzw, angular velocity `v[i .. i + 2]` in
+ *   the joint frame), 7 free-flyer (`q`: position 3, quaternion 4; `v`: linear 3, angular 3, both local), 8 / 9 / 10
+ *   prismatic along x / y / z, 11 prismatic along `seg_axis`.  The placement of a segment with a joint is the placement of
+ *   that joint alone, so that `model_lane` can replace its translation.  jm_frames_plan_create validates the description
+ *   (JM_EINVAL + jm_last_error, before any device call: null arrays, sizes, segment counts, `q` / `v` rows, joint indices in
+ *   `[0, njoints)`, kinds, modes, finite constants) and uploads it; the two calls then allocate, copy and synchronise nothing.
+ * jm_block_frame_kinematics: on the lanes of `lane_mask` (device, uint8 `[B]`; NULL: every lane; other lanes are not
+ *   touched) writes, each or NULL, `pose` `[7][K][B]` (x y z, quaternion xyzw by the `matrices_to_quat` rule), `pose_prev`
+ *   `[7][K][B]` (the same pose: the reset of the step average), `rpy` `[3][K][B]` (`quat_to_rpy`) and `vel` `[6][K][B]`
+ *   (linear, angular, in the convention of pinocchio's `getFrameVelocity`: LOCAL `(R^T pdot, R^T omega)`, LOCAL_WORLD_ALIGNED
+ *   `(pdot, omega)`, pdot the velocity of the frame origin; needs `v`).  `model_lane` (JM_F_MODEL_LANE `[13 * njoints][B]`,
+ *   or NULL): the translation of the placement of joint j is rows `13 j + 10 .. 13 j + 12` of the lane.
+ *   ≙ `FramePosition`, `FrameOrientation`, `FrameXYZQuat` (python/gym_jiminy/common/gym_jiminy/common/quantities/generic.py:298-950).
+ * jm_block_frame_average: per lane and frame `diff = xyzquat_difference(pose_prev, pose)` (utils/math.py:1009-1042, with
+ *   `log6` :842-894 and `log3` :725-774), `pose_mean = pose * exp6(-diff / 2)` (`exp6` :908-954, `exp3` :791-825;
+ *   `AverageFrameXYZQuat`, generic.py:1357-1360), `quat_no_yaw = remove_yaw_from_quat(quaternion of pose_mean)` (:1148-1198;
+ *   `AverageFrameRollPitch`), `v_avg = diff * inv_step_dt` with both halves rotated by nothing (LOCAL), the mean quaternion
+ *   (LOCAL_WORLD_ALIGNED, generic.py:1522-1534) or `quat_no_yaw` (ODOMETRY, quantities/locomotion.py:281-288); last `pose` is
+ *   copied into `pose_prev`.  `v_avg` `[6][K][B]`, `pose_mean` `[7][K][B]`, `quat_no_yaw` `[4][K][B]`, each or NULL.  The clamps
+ *   of the divisions are `tiny` of the kernel's own scalar type: two identical poses give a zero difference and an
+ *   unchanged mean in float32 as well.  `pose_prev` must not alias `pose`. */
+typedef struct jm_frames_desc
+{
+    int32_t n_frames;
+    int32_t nq;                         /* rows of q: the range of seg_q_index */
+    int32_t nv;                         /* rows of v: the range of seg_v_index */
+    int32_t njoints;                    /* the range of seg_joint */
+    const int32_t * frame_seg_start;    /* [n_frames + 1], ascending, last = n_seg */
+    const int32_t * frame_mode;         /* [n_frames] */
+    int32_t n_seg;
+    const int32_t * seg_kind;           /* [n_seg] */
+    const int32_t * seg_joint;          /* [n_seg], -1 where seg_kind is 0 */
+    const int32_t * seg_q_index;        /* [n_seg], -1 where seg_kind is 0 */
+    const int32_t * seg_v_index;        /* [n_seg], -1 where seg_kind is 0 */
+    const double * seg_rot;             /* [n_seg][9] */
+    const double * seg_trans;           /* [n_seg][3] */
+    const double * seg_axis;            /* [n_seg][3] */
+} jm_frames_desc;
+typedef struct jm_frames_plan jm_frames_plan;
+int32_t jm_frames_plan_create(const jm_frames_desc * desc, jm_frames_plan ** out);
+int32_t jm_frames_plan_destroy(jm_frames_plan * plan);
+int32_t jm_block_frame_kinematics(const jm_frames_plan * plan, int32_t dtype, int64_t batch_size, const void * q,
+                                  const void * v, const void * model_lane, const uint8_t * lane_mask, void * pose,
+                                  void * pose_prev, void * rpy, void * vel, void * stream);
+int32_t jm_block_frame_average(const jm_frames_plan * plan, int32_t dtype, int64_t batch_size, void * pose_prev,
+                               const void * pose, double inv_step_dt, void * v_avg, void * pose_mean, void * quat_no_yaw,
+                               void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

@@ -99,6 +99,16 @@ class AttitudeDesc(C.Structure):
     ]
 
 
+class FramesDesc(C.Structure):
+    """jm_frames_desc: the plan of the frame kinematics block (jiminy_amd.frames builds it)."""
+    _fields_ = [
+        ("n_frames", C.c_int32), ("nq", C.c_int32), ("nv", C.c_int32), ("njoints", C.c_int32),
+        ("frame_seg_start", _pi), ("frame_mode", _pi),
+        ("n_seg", C.c_int32), ("seg_kind", _pi), ("seg_joint", _pi), ("seg_q_index", _pi), ("seg_v_index", _pi),
+        ("seg_rot", _pd), ("seg_trans", _pd), ("seg_axis", _pd),
+    ]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

@@ -1,5 +1,5 @@
-"""What the plan builders of the observer blocks share (deformation.py, attitude.py): the rotation segments of a frame
-and the marshalling of a plan description."""
+"""What the plan builders of the observer blocks and of the frame kinematics share (deformation.py, attitude.py, frames.py):
+the segments of a frame and the marshalling of a plan description."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,6 +12,8 @@ from .model import JT_RU, JT_RX, JT_RY, JT_RZ, CompiledModel
 # joint kinds of a plan segment (include/jiminy_hip.h: jm_deform_desc knows the first five, jm_attitude_desc all)
 SEG_NONE, SEG_X, SEG_Y, SEG_Z, SEG_AXIS, SEG_UNBOUNDED, SEG_QUAT = range(7)
 AXIS_KIND = {JT_RX: SEG_X, JT_RY: SEG_Y, JT_RZ: SEG_Z, JT_RU: SEG_AXIS}
+# further kinds of jm_frames_desc, where SEG_QUAT is the spherical joint alone
+SEG_FREEFLYER, SEG_PX, SEG_PY, SEG_PZ, SEG_PAXIS = range(7, 12)
 
 
 class SegmentTable:
@@ -51,6 +53,40 @@ class SegmentTable:
         const = const @ np.asarray(R_frame, dtype=np.float64)
         if len(self.kind) == self.frame_seg_start[-1] or not np.array_equal(const, np.eye(3)):
             self._append(const, SEG_NONE, -1, np.zeros(3), 0.0)
+        self.frame_seg_start.append(len(self.kind))
+        return len(self.frame_seg_start) - 2
+
+
+class PlacedSegmentTable(SegmentTable):
+    """Frames as lists of segments with translations: a segment is a constant placement (rotation, translation) followed by
+    the motion of one joint, of which the table also keeps the index and the first row of `v` (`index` is the first row of
+    `q`).  Every joint of the path is a segment of its own, so that the placement of a segment is the placement of its joint
+    alone; the trailing constant segment, always emitted, is the placement of the frame on its parent joint."""
+
+    def __init__(self) -> None:
+        super().__init__()
+        self.trans: List[np.ndarray] = []
+        self.joint: List[int] = []
+        self.v_index: List[int] = []
+
+    def add_placed_frame(self, model: CompiledModel, joint: int, R_frame, p_frame,
+                         joint_segment: Callable[[int], tuple]) -> int:
+        """Walk from the universe to the frame attached to `joint` with placement (`R_frame`, `p_frame`);
+        `joint_segment(j)` gives (kind, first q row, first v row, axis) of joint j.  Returns the index of the frame."""
+        path, j = [], joint
+        while j != 0:
+            path.append(j)
+            j = int(model.parents[j])
+        for j in reversed(path):
+            kind, iq, iv, axis = joint_segment(j)
+            self._append(np.asarray(model.placement_R[j], dtype=np.float64), kind, iq, axis, 0.0)
+            self.trans.append(np.asarray(model.placement_p[j], dtype=np.float64))
+            self.joint.append(j)
+            self.v_index.append(iv)
+        self._append(np.asarray(R_frame, dtype=np.float64), SEG_NONE, -1, np.zeros(3), 0.0)
+        self.trans.append(np.asarray(p_frame, dtype=np.float64))
+        self.joint.append(-1)
+        self.v_index.append(-1)
         self.frame_seg_start.append(len(self.kind))
         return len(self.frame_seg_start) - 2
 

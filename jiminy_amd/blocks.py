@@ -23,6 +23,10 @@ It has no tensor-program form: its specification is the reference's own output (
 (blocks/mahony_filter.py:104-393, blocks/body_orientation_observer.py:74-266): per-IMU gains, twist removal, Euler angles, the
 initialisation at the first refresh of an episode, the body frames and the leaky twist integrator.  One HIP launch per
 refresh (csrc/jm_attitude.h) driven by a plan that jiminy_amd/attitude.py builds; specification: tests/golden/ref_attitude.npz.
+
+`FrameKinematics` gives the pose and the velocity of named frames and their SE3 average over an environment step (what the
+reference's quantity layer reads from `pinocchio_data.oMf` and `getFrameVelocity`): one HIP launch each (csrc/jm_frames.h) driven
+by a plan that jiminy_amd/frames.py builds; specification of the average: tests/golden/ref_frames.npz.
 """
 from __future__ import annotations
 
@@ -351,6 +355,132 @@ class BodyObserver:
         m._check(m._L.jm_block_body_observer(
             m._plan, m._dtype, eng.batch_size, m._vp(m.quat), m._vp(m.omega), m._vp(quat), m._vp(omega),
             m._vp(self.twist), int(mode), float(tci), float(dt), m._vp(rpy), eng._stream()))
+
+
+def frame_fieldnames(frame_names, compute_rpy: bool, compute_velocity: bool, average: bool):
+    """Names of the rows of the tensors of a `FrameKinematics` block, `[row][frame]` per tensor."""
+    fr = list(frame_names)
+    pose = ("X", "Y", "Z", "QuatX", "QuatY", "QuatZ", "QuatW")
+    spatial = ("LinX", "LinY", "LinZ", "AngX", "AngY", "AngZ")
+    names = {"pose": [[f"{n}.{e}" for n in fr] for e in pose]}
+    if compute_rpy:
+        names["rpy"] = [[f"{n}.{e}" for n in fr] for e in ("Roll", "Pitch", "Yaw")]
+    if compute_velocity:
+        names["velocity"] = [[f"{n}.{e}" for n in fr] for e in spatial]
+    if average:
+        names["average_velocity"] = [[f"{n}.{e}" for n in fr] for e in spatial]
+        names["pose_mean"] = [[f"{n}.{e}" for n in fr] for e in pose]
+        names["quat_no_yaw"] = [[f"{n}.Quat{e}" for n in fr] for e in ("X", "Y", "Z", "W")]
+    return names
+
+
+class FrameKinematics:
+    """Pose and velocity of named frames of the engine's model, per lane, and their average over an environment step.
+
+    ≙ `FramePosition` / `FrameOrientation` / `FrameXYZQuat` (quantities/generic.py:298-950) for `pose` `[7][K][B]` (x y z,
+    quaternion xyzw) and `rpy` `[3][K][B]` (`compute_rpy`, else None), pinocchio's `getFrameVelocity` for `velocity`
+    `[6][K][B]` (linear, angular; `compute_velocity`, else None) in the reference frame of every frame (`reference_frames`:
+    "LOCAL" (default), "LOCAL_WORLD_ALIGNED" or, with `average`, "ODOMETRY", whose instantaneous velocity is LOCAL).
+    With `average`: `average_velocity` `[6][K][B]` ≙ `FrameSpatialAverageVelocity` (:1429-1534) and, for ODOMETRY frames,
+    `BaseSpatialAverageVelocity` (quantities/locomotion.py:222-288); `pose_mean` `[7][K][B]` ≙ `AverageFrameXYZQuat`
+    (:1289-1360); `quat_no_yaw` `[4][K][B]` ≙ `AverageFrameRollPitch` (:1363-1426).
+
+    `reset(lane_mask)` evaluates the frames at the state the engine's `start` / `reset_lanes` wrote and makes it the previous
+    pose of the average; `refresh()` evaluates them at the engine's current `q`, `v` (with the per-lane joint placements when
+    the engine has a biased model bound); `refresh_average(step_dt)` averages between the pose of the previous call (or
+    reset) and the current `pose`.  One launch each, no allocation, copy or synchronisation; the tensors never change
+    identity."""
+
+    def __init__(self, engine, frame_names, *, reference_frames=None, compute_rpy: bool = False, compute_velocity: bool = True,
+                 average: bool = False) -> None:
+        import ctypes as C
+
+        from . import _abi, frames
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.plan = frames.build_plan(engine.model, frame_names, reference_frames)
+        self.frame_names = list(self.plan.frame_names)
+        self.compute_rpy, self.compute_velocity, self.average = bool(compute_rpy), bool(compute_velocity), bool(average)
+        if not self.average and frames.ODOMETRY in self.plan.modes:
+            raise NotImplementedError("the ODOMETRY reference frame is defined for the step average only: pass average=True")
+        K, B = self.plan.n_frames, engine.batch_size
+        new = lambda rows: torch.zeros((rows, K, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
+        self.pose = new(7)
+        self.pose[6] = 1.0
+        self.rpy = new(3) if self.compute_rpy else None
+        self.velocity = new(6) if self.compute_velocity else None
+        self.average_velocity = self.pose_mean = self.quat_no_yaw = self.pose_prev = None
+        if self.average:
+            self.average_velocity, self.pose_mean, self.quat_no_yaw, self.pose_prev = new(6), new(7), new(4), new(7)
+            for t in (self.pose_mean[6], self.quat_no_yaw[3], self.pose_prev[6]):
+                t.fill_(1.0)
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_frames_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    def index(self, frame_name: str) -> int:
+        """Column of a frame in the tensors."""
+        return self.frame_names.index(frame_name)
+
+    @property
+    def fieldnames(self):
+        return frame_fieldnames(self.frame_names, self.compute_rpy, self.compute_velocity, self.average)
+
+    def _vp(self, t: Optional[torch.Tensor]):
+        if t is None:
+            return None
+        _check_block_tensor(self._eng, t)
+        return self._C.c_void_p(t.data_ptr())
+
+    def _kinematics(self, mask: Optional[torch.Tensor], pose_prev: Optional[torch.Tensor]) -> None:
+        eng = self._eng
+        model_lane = eng._fields.get("model_lane")
+        self._check(self._L.jm_block_frame_kinematics(
+            self._plan, self._dtype, eng.batch_size, self._vp(eng.field("q")),
+            self._vp(eng.field("v")) if self.compute_velocity else None, self._vp(model_lane),
+            None if mask is None else self._C.c_void_p(mask.data_ptr()), self._vp(self.pose), self._vp(pose_prev),
+            self._vp(self.rpy), self._vp(self.velocity), eng._stream()))
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The frames at the state of a new episode on the masked lanes (every lane without a mask), which also becomes
+        the previous pose of their step average.  The other lanes keep every tensor bit for bit.  Call it after the
+        engine's `start` / `reset_lanes`."""
+        eng = self._eng
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        self._kinematics(mask, self.pose_prev)
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream: `pose`, `rpy`, `velocity` at the engine's `q`, `v`."""
+        self._kinematics(None, None)
+
+    def refresh_average(self, step_dt: float) -> None:
+        """One launch: `average_velocity`, `pose_mean`, `quat_no_yaw` between the previous pose and `pose`, which then
+        becomes the previous one."""
+        if not self.average:
+            raise RuntimeError("this block was built without average=True")
+        if not step_dt > 0.0:
+            raise ValueError("the step average needs a positive step_dt")
+        eng = self._eng
+        self._check(self._L.jm_block_frame_average(
+            self._plan, self._dtype, eng.batch_size, self._vp(self.pose_prev), self._vp(self.pose), 1.0 / float(step_dt),
+            self._vp(self.average_velocity), self._vp(self.pose_mean), self._vp(self.quat_no_yaw), eng._stream()))
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_frames_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
 
 
 def integrate_zoh(state: torch.Tensor, state_min: torch.Tensor, state_max: torch.Tensor,

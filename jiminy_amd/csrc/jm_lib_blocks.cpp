@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families and of the frame kinematics, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "jm_blocks.h"
 #include "jm_deform.h"
 #include "jm_attitude.h"
+#include "jm_frames.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -84,6 +85,11 @@ struct jm_attitude_plan
 {
     DevicePlan dev;
     int n_imu = 0;
+};
+// frame kinematics and its step average (jm_frames.h)
+struct jm_frames_plan
+{
+    DevicePlan dev;
 };
 
 extern "C"
@@ -263,6 +269,49 @@ int32_t jm_block_body_observer(const jm_attitude_plan * p, int32_t dtype, int64_
         hipLaunchKernelGGL((jm::k_body_observer<T>), grid, dim3(256), 0, s, a, (const T *)imu_quat,
                            (const T *)imu_omega, (T *)quat, (T *)omega, (T *)twist, (int)twist_mode,
                            time_constant_inv, dt, (T *)rpy, (long long)B);
+    });
+}
+
+int32_t jm_frames_plan_create(const jm_frames_desc * desc, jm_frames_plan ** out)
+{
+    return plan_create("jm_frames_plan_create", desc, out, jm::frames_pack);
+}
+
+int32_t jm_frames_plan_destroy(jm_frames_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_frame_kinematics(const jm_frames_plan * p, int32_t dtype, int64_t B, const void * q, const void * v,
+                                  const void * model_lane, const uint8_t * lane_mask, void * pose, void * pose_prev, void * rpy,
+                                  void * vel, void * stream)
+{
+    if (!p || !q) return fail(JM_EINVAL, "jm_block_frame_kinematics: null argument");
+    if (vel && !v) return fail(JM_EINVAL, "jm_block_frame_kinematics: the frame velocity needs v");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_frame_kinematics: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_frame_kinematics: bad dtype");
+    if (pose && pose == pose_prev) return fail(JM_EINVAL, "jm_block_frame_kinematics: pose_prev must not alias pose");
+    const jm::FramesArgs a{p->dev.it, p->dev.dt};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_frame_kinematics<T>), grid, dim3(256), 0, s, a, (const T *)q, (const T *)v,
+                           (const T *)model_lane, lane_mask, (T *)pose, (T *)pose_prev, (T *)rpy, (T *)vel, (long long)B);
+    });
+}
+
+int32_t jm_block_frame_average(const jm_frames_plan * p, int32_t dtype, int64_t B, void * pose_prev, const void * pose,
+                               double inv_step_dt, void * v_avg, void * pose_mean, void * quat_no_yaw, void * stream)
+{
+    if (!p || !pose_prev || !pose) return fail(JM_EINVAL, "jm_block_frame_average: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_frame_average: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_frame_average: bad dtype");
+    if (pose_prev == pose) return fail(JM_EINVAL, "jm_block_frame_average: pose_prev must not alias pose");
+    const jm::FramesArgs a{p->dev.it, p->dev.dt};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_frame_average<T>), grid, dim3(256), 0, s, a, (T *)pose_prev, (const T *)pose, inv_step_dt,
+                           (T *)v_avg, (T *)pose_mean, (T *)quat_no_yaw, (long long)B);
     });
 }
 

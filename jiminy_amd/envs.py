@@ -427,9 +427,38 @@ class WalkerVecEnv(VecJiminyEnv):
     `std_ratio['model']` randomises the flexibility stiffness / damping of every environment per episode
     (locomotion.py:288-296, `VecJiminyEnv._randomise_flexibility`)."""
 
-    def __init__(self, *args: Any, reward_mixture: Optional[Dict[str, float]] = None, **kw: Any) -> None:
+    def __init__(self, *args: Any, reward_mixture: Optional[Dict[str, float]] = None,
+                 frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
+                 **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
+        # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
+        # environment step behind the physics and exposed as `frames`; and the first two terminations that read it, or-ed
+        # into `has_terminated`:
+        #   base_roll_pitch=(low, high, grace_period)  ≙ `BaseRollPitchTermination` (compositions/locomotion.py:318-355)
+        #   min_base_height=(value, grace_period)      ≙ `FallingTermination` (:358-398) on `base_relative_height()`
+        # a lane terminates when its episode time has reached the grace period and the value has left [low, high]
+        # (bases/compositions.py:560-571, 647-663).  With both None nothing of this exists.
+        self.frames = None
+        self._terminations = dict(terminations or {})
+        unknown = set(self._terminations) - {"base_roll_pitch", "min_base_height"}
+        if unknown:
+            raise ValueError(f"unknown terminations {sorted(unknown)} (base_roll_pitch, min_base_height)")
+        if self._terminations and frame_kinematics is None:
+            raise ValueError("the terminations read the frame kinematics block: give frame_kinematics as well")
+        if frame_kinematics is not None:
+            names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, self._terminations)
+            self.frames = blocks.FrameKinematics(self.engine, names, reference_frames=modes, **cfg)
+            if self._terminations:
+                self._frame_root = self.frames.index("root_joint")
+                self._frame_contacts = torch.tensor([self.frames.index(n) for n in self.model.contacts], dtype=torch.long, device=self.device)
+                if "base_roll_pitch" in self._terminations:
+                    # (a bound is one number for both angles or one per angle)
+                    low, high, grace = self._terminations["base_roll_pitch"]
+                    bound = lambda x: torch.as_tensor(x, dtype=self.dtype, device=self.device).reshape(-1, 1)     # noqa: E731
+                    self._roll_pitch_bounds = (bound(low), bound(high), float(grace))
+                if "min_base_height" in self._terminations and not self.model.contacts:
+                    raise ValueError("min_base_height needs a model with contact frames")
         m = self.model
         lim = torch.tensor([mo.effort_limit * mo.velocity_limit for mo in m.motors], dtype=self.dtype)
         self._power_consumption_max = float(lim.sum())  # locomotion.py:230-236
@@ -444,6 +473,28 @@ class WalkerVecEnv(VecJiminyEnv):
         self._dir_sum = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
         self._dir_n = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
 
+    @staticmethod
+    def frame_kinematics_config(model: CompiledModel, frame_kinematics: Dict[str, Any], terminations: Dict[str, Any]
+                                ) -> Tuple[list, Optional[list], Dict[str, Any]]:
+        """Frame names, reference frames and remaining keywords of the `blocks.FrameKinematics` of an environment: the
+        user's, plus what the terminations read where it is missing -- the root joint and every contact frame (LOCAL), and
+        the Euler angles for `base_roll_pitch`."""
+        cfg = dict(frame_kinematics)
+        names = list(cfg.pop("frame_names", ()))
+        modes = cfg.pop("reference_frames", None)
+        modes = None if modes is None else list(modes)
+        if modes is not None and len(modes) != len(names):
+            raise ValueError(f"expected one reference frame per frame ({len(names)}), got {len(modes)}")
+        if terminations:
+            for name in ["root_joint"] + list(model.contacts):
+                if name not in names:
+                    names.append(name)
+                    if modes is not None:
+                        modes.append("LOCAL")
+            if "base_roll_pitch" in terminations:
+                cfg["compute_rpy"] = True
+        return names, modes, cfg
+
     def _direction_restart(self, lane_mask: Optional[torch.Tensor]) -> None:
         y0 = self.engine.robot_state.q[1].to(torch.float64)
         if lane_mask is None:
@@ -456,21 +507,47 @@ class WalkerVecEnv(VecJiminyEnv):
     def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
         out = super().reset(seed, options)
         self._direction_restart(None)
+        if self.frames is not None:
+            self.frames.reset(None)
         return out
 
     def reset_lanes(self, lane_mask: torch.Tensor) -> None:
         super().reset_lanes(lane_mask)
         self._direction_restart(lane_mask)
+        if self.frames is not None:
+            self.frames.reset(lane_mask)
 
     def _after_step(self):
         self._dir_sum += self.engine.robot_state.q[1].to(torch.float64)
         self._dir_n += 1.0
+        if self.frames is not None:
+            self.frames.refresh()
+            if self.frames.average:
+                self.frames.refresh_average(self.step_dt)
         return super()._after_step()
+
+    def base_relative_height(self) -> torch.Tensor:
+        """≙ `BaseRelativeHeight` (quantities/locomotion.py:88-97, 153-154): height of the root joint over the lowest contact
+        frame, per lane, from the poses of the frame kinematics block."""
+        if self.frames is None or not self._terminations:
+            raise RuntimeError("base_relative_height needs frame_kinematics and terminations")
+        z = self.frames.pose[2]
+        return z[self._frame_root] - z[self._frame_contacts].min(0).values
 
     def has_terminated(self) -> Tuple[torch.Tensor, torch.Tensor]:
         terminated, truncated = super().has_terminated()
         z = self.engine.robot_state.q[2]
-        return terminated | (z < 0.5 * self._height_neutral), truncated  # locomotion.py:381-383
+        terminated = terminated | (z < 0.5 * self._height_neutral)  # locomotion.py:381-383
+        if self._terminations:
+            t = self._lane_time()
+            if "base_roll_pitch" in self._terminations:
+                low, high, grace = self._roll_pitch_bounds
+                rp = self.frames.rpy[:2, self._frame_root]
+                terminated = terminated | ((t >= grace) & ((rp < low) | (rp > high)).any(0))
+            if "min_base_height" in self._terminations:
+                value, grace = self._terminations["min_base_height"]
+                terminated = terminated | ((t >= grace) & (self.base_relative_height() < value))
+        return terminated, truncated
 
     def compute_reward(self, terminated: torch.Tensor) -> torch.Tensor:
         total = torch.zeros(self.num_envs, dtype=self.dtype, device=self.device)
@@ -706,6 +783,9 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
             if whole_step and (not self.auto_reset or float(self.std_ratio.get("ground", 0.0)) > 0.0 or
                                self._ground_patch_extent is not None):
                 raise NotImplementedError("whole-step graphs need auto_reset and no ground-friction / terrain-patch randomisation")
+            if whole_step and self.frames is not None:
+                raise NotImplementedError("whole-step graphs do not take the frame kinematics block: its reset is not part "
+                                          "of the captured step")
             if whole_step and self._mahony is not None:
                 raise NotImplementedError("whole-step graphs do not take the MahonyFilter / BodyObserver blocks: their "
                                           "initialisation at reset is not part of the captured step")
