@@ -297,14 +297,7 @@ def qcon_split(model: CompiledModel) -> bool:
     nb = sum(1 for t in model.jtypes[1:] if 1 <= int(t) <= 8)
     # ... or whose whole solve fits the fixed 16-row layout of the one-lane-per-robot solve (`jm::qcon_split_lane`, round 6)
     lane = 1 <= model.ncontacts and 3 * model.ncontacts <= 16
-    return min(nb + 4 * model.ncontacts, 96) > qcon_split_min() or lane
-
-
-def qcon_split_min() -> int:
-    """Solves of more rows than this step through pre | solve | post launches (`JM_QCON_SPLIT_MIN` of jm_qcon.h, 32).
-    JIMINY_AMD_QCON_SPLIT_MIN builds an experimental library with another threshold (use with JIMINY_AMD_LIB_TAG: round 5
-    measured ANYmal -- 28 rows -- in the split form)."""
-    return int(os.environ.get("JIMINY_AMD_QCON_SPLIT_MIN", "32"))
+    return min(nb + 4 * model.ncontacts, 96) > 32 or lane
 
 
 # Flags every topology compiles a unit with.  Unit 1 (the one-robot-per-lane constraint kernel): without the IR
@@ -340,9 +333,7 @@ def lib_path(model: CompiledModel, variant: Optional[int] = None) -> str:
 
 
 def header_path(model: CompiledModel) -> str:
-    # (experimental builds that change what the header says keep a header of their own)
-    tag = os.environ.get("JIMINY_AMD_LIB_TAG", "") if qcon_split_min() != 32 else ""
-    return os.path.join(BUILD, f"topo_{model.topology_hash()}{('_' + tag) if tag else ''}.h")
+    return os.path.join(BUILD, f"topo_{model.topology_hash()}.h")
 
 
 def write_header(model: CompiledModel) -> str:
@@ -452,8 +443,6 @@ def build_library(model: CompiledModel, force: bool = False, verbose: bool = Fal
     common = COMMON_FLAGS + [f"-DJM_TOPO_HEADER=\"{hdr}\""]
     common += list(BUILD_VARIANTS[v])
     common += extra_flags or []
-    if qcon_split_min() != 32:
-        common.append(f"-DJM_QCON_SPLIT_MIN={qcon_split_min()}")
     # (15, 16: the one-robot-per-lane kernels in the form that reads applied wrenches -- topologies without branch-parallel kernels)
     parts = [1, 2, 3, 4, 5, 6, 11, 12] if quad_structure(model) is not None else [1, 15, 16]
     if qcon_split(model):

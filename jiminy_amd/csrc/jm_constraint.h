@@ -28,25 +28,6 @@
 #pragma once
 #include "jm_kernels.h"
 
-// tuning switches (A/B measurements)
-#ifndef JM_CON_MASKS
-#define JM_CON_MASKS 1  // path-restricted sweeps of the bias-free solves
-#endif
-#ifndef JM_CON_REBUILD
-#define JM_CON_REBUILD 1  // rebuild liMi in the bias-free solves instead of reading it back from scratch
-#endif
-#ifndef JM_CON_PGS_REG
-#define JM_CON_PGS_REG 0   // robots with <= 32 constraint rows: PGS vectors in registers, fully unrolled sweeps
-                          // (measured slower: every lane pays for all NR x NR predicated slots, + 7 kB of scratch)
-#endif
-#ifndef JM_CON_XALIAS
-#define JM_CON_XALIAS 1  // PGS multipliers in the (unused) RK stage rows of LDS for non-RK4 launches
-#endif
-#ifndef JM_CON_XLDS
-#define JM_CON_XLDS 0   // packed multipliers in LDS during the PGS solve (faster solve, but the extra 14 kB
-                        // per block cost one resident wave per CU: measured slower on warm-started workloads)
-#endif
-
 namespace jm
 {
 template<class T> struct ConArgs
@@ -254,7 +235,6 @@ template<class Tp, class F> JM_DEV void for_contacts(F && f)
 // (scalar loads): the column solves are bound by the traffic of the spilled working set, not by flops
 template<class T, class Tp, int J, class WC> JM_DEV SE3<T> limi_rebuilt(CPtr<T> P, const WC & w)
 {
-#if JM_CON_REBUILD
     using L = Layout<Tp>;
     constexpr int t = Tp::jtype[J];
     if constexpr (jt_is_sph(t)) return w.liMi[J];
@@ -273,9 +253,6 @@ template<class T, class Tp, int J, class WC> JM_DEV SE3<T> limi_rebuilt(CPtr<T> 
         Mj.p = w.jcs[J][0] * joint_axis<T, Tp, J>(P);
     }
     return plc * Mj;
-#else
-    return w.liMi[J];
-#endif
 }
 
 // depth of a joint in the tree (joints hanging from the universe: 1)
@@ -341,7 +318,7 @@ JM_DEV void delta_sweeps(CPtr<T> P, const WC & w, FT && tau, FB && fb, VIS && vi
                 acc[d - 1] = acc[d - 1] + act_force(limi_rebuilt<T, Tp, j>(P, w), pa);
             }
         }
-        else if (!JM_CON_MASKS || ((bmask >> j) & 1ull))
+        else if ((bmask >> j) & 1ull)
         {
             const Sp<T> pf = acc[d] - fb(jc);
             acc[d] = zero6<T>();
@@ -382,7 +359,7 @@ JM_DEV void delta_sweeps(CPtr<T> P, const WC & w, FT && tau, FB && fb, VIS && vi
             lvl[d] = {ag.l, ag.a + dd};
             visit(jc, b, lvl[d]);
         }
-        else if (!JM_CON_MASKS || ((fmask >> j) & 1ull))
+        else if ((fmask >> j) & 1ull)
         {
             Sp<T> ag;
             if constexpr (p > 0) ag = actinv_motion(limi_rebuilt<T, Tp, j>(P, w), lvl[d - 1]);
@@ -583,125 +560,6 @@ JM_DEV bool pgs_solve_packed(const ConArgs<T> & C, T friction, int m, int nb, WS
     }
     for (int r = 0; r < m; ++r) ws(R::WX + r) = xl[r * xs];
     return false;
-}
-
-// The same solve for robots with at most 32 constraint rows (ANYmal: 28): the sweeps are unrolled on
-// compile-time packed indices, so that x, b, y live in registers (no store -> load round trip through memory
-// between two row updates of the Gauss-Seidel chain) and every delassus entry sits at a constant offset: the
-// loads of the next rows do not depend on the multipliers being updated and are issued ahead of them.
-// Rows beyond the lane's m and rows of another block are skipped by run-time predicates; the arithmetic and
-// its order are those of pgs_solve_packed.
-template<class T, class Tp, class WS>
-JM_DEV bool pgs_solve_regs(const ConArgs<T> & C, T friction, int m, int nb, WS && ws)
-{
-    using R = ConRows<Tp>;
-    constexpr int NR = R::NR;
-    const T eps = Eps<T>::eps;
-    T x[NR], bb[NR], y[NR], yp[NR];
-    static_for<0, NR>([&](auto pc) {
-        constexpr int p = decltype(pc)::value;
-        x[p] = p < m ? ws(R::WX + p) : T(0);
-        bb[p] = p < m ? ws(R::WB + p) : T(0);
-        y[p] = T(0);
-    });
-    auto col_dot = [&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        T s = T(0);
-        static_for<0, NR>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            const T a = k < m ? ws(R::WA + k * NR + i) : T(0);
-            s += a * x[k];
-        });
-        return s;
-    };
-    const bool torsion_zero = C.torsion < eps, friction_zero = friction < eps;
-    const unsigned iter_max = (unsigned)C.iter_max;
-    bool converged = false;
-#pragma nounroll
-    for (unsigned iter = 0; iter < iter_max && !converged; ++iter)
-    {
-        static_for<0, NR>([&](auto pc) { yp[decltype(pc)::value] = y[decltype(pc)::value]; });
-        const T ratio = (T(iter_max - 20u) - T(iter)) / T(iter_max - 20u - 30u);
-        T w = T(1);
-        if (ratio < T(1))
-        {
-            w = T(0.01);
-            if (ratio > T(0)) w += (T(1) - T(0.01)) * (ratio * ratio);
-        }
-        // the three block passes of the reference (0: bounds + normals, 1: torsion, 2: friction cones) as a
-        // run-time loop around ONE unrolled visit of the rows: a row acts in the pass its kind belongs to.
-        // The residual of the first row of a friction pair is parked until its partner has its own (both
-        // are taken before either multiplier moves, constraint_solvers.cc:175-195).
-#pragma nounroll
-        for (int blk = 0; blk < 3; ++blk)
-        {
-            T y0_pair = T(0);
-            static_for<0, NR>([&](auto pc) {
-                constexpr int p = decltype(pc)::value;
-                const int dof = (p - nb) & 3;  // 0..3 = x, y, z (normal), torsion for the rows of a contact
-                const bool bound = p < nb;
-                const int kind = bound ? 0 : (dof == 2 ? 0 : (dof == 3 ? 1 : 2));
-                if (p < m && kind == blk)
-                {
-                    if (blk == 1 && torsion_zero) x[p] = x[p] * T(0);
-                    else if (blk == 2 && friction_zero) x[p] = x[p] * T(0);
-                    else
-                    {
-                        const T yy = bb[p] - col_dot(pc);
-                        y[p] = yy;
-                        const T app = ws(R::WA + p * NR + p);
-                        if (blk == 0) x[p] = fmax_(x[p] + w * yy / app, T(0));
-                        else if (blk == 1)
-                        {
-                            if constexpr (p >= 1)
-                            {
-                                const T thr = C.torsion * x[p - 1];
-                                x[p] = clamp_(x[p] + w * yy / app, -thr, thr);
-                            }
-                        }
-                        else if (dof == 0) y0_pair = yy;
-                        else
-                        {
-                            if constexpr (p >= 1 && p + 1 < NR)
-                            {
-                                const T a00 = ws(R::WA + (p - 1) * NR + p - 1);
-                                const T a_max = app > a00 ? app : a00;
-                                T e0 = x[p - 1] + w * y0_pair / a_max;
-                                T e1 = x[p] + w * yy / a_max;
-                                const T thr = friction * x[p + 1];
-                                const T n2 = e0 * e0 + e1 * e1;
-                                if (n2 > thr * thr)
-                                {
-                                    const T scale = thr / sqrt_(n2);
-                                    e0 *= scale;
-                                    e1 *= scale;
-                                }
-                                x[p - 1] = e0;
-                                x[p] = e1;
-                            }
-                        }
-                    }
-                }
-            });
-        }
-        T ymax = T(0);
-        static_for<0, NR>([&](auto pc) {
-            constexpr int p = decltype(pc)::value;
-            if (p < m) ymax = fmax_(ymax, cabs_(y[p]));
-        });
-        const T tol = C.tol_abs + C.tol_rel * ymax + eps;
-        bool done = true;
-        static_for<0, NR>([&](auto pc) {
-            constexpr int p = decltype(pc)::value;
-            if (p < m) done &= cabs_(y[p] - yp[p]) < tol;
-        });
-        converged = done;
-    }
-    static_for<0, NR>([&](auto pc) {
-        constexpr int p = decltype(pc)::value;
-        if (p < m) ws(R::WX + p) = x[p];
-    });
-    return converged;
 }
 
 // ---- kinds of user constraint frames (JM_XKIND_*): what differs from the plain FrameConstraint rows
@@ -1334,10 +1192,9 @@ JM_DEV void eval_constrained(CPtr<T> P, const T * q, const T * v, const T * cmd,
             {
                 if (C.park)
                 for (int r = 0; r < C.park_rows; ++r) C.park[(size_t)r * B] = C.xl[r * C.xstride];
-            // (the register form of the sweeps knows no unbounded rows: solves with any go through the general form)
-            if constexpr (JM_CON_PGS_REG && NR <= 32) ok = lockp ? pgs_solve_packed<T, Tp>(C, friction, m_act, nb_act, ws, lockp, mc_act)
-                                                               : pgs_solve_regs<T, Tp>(C, friction, m_act, nb_act, ws);
-            else ok = pgs_solve_packed<T, Tp>(C, friction, m_act, nb_act, ws, lockp, mc_act);
+            // (a form for robots with <= 32 rows, PGS vectors in registers and fully unrolled sweeps, measured slower: every
+            // lane pays for all NR x NR predicated slots, + 7 kB of scratch -- DESIGN.md section 4.8)
+            ok = pgs_solve_packed<T, Tp>(C, friction, m_act, nb_act, ws, lockp, mc_act);
             if (C.park)
                 for (int r = 0; r < C.park_rows; ++r) C.xl[r * C.xstride] = C.park[(size_t)r * B];
                 if (ok) w.status &= ~JM_LANE_SOLVER_FAILURE;
@@ -1547,21 +1404,16 @@ __global__ void __launch_bounds__(64) k_constrained(const BatchArgs<T> A, const 
     const long long lane = (long long)blockIdx.x * 64 + threadIdx.x;
     if (lane >= A.B) return;
     ConArgs<T> Cl = C;
-#if JM_CON_XLDS
-    __shared__ T xs[(ConRows<Tp>::NR > 0 ? ConRows<Tp>::NR : 1) * 64];
-    Cl.xl = xs + threadIdx.x;
-    Cl.xstride = 64;
-    Cl.yl = nullptr; Cl.ystride = 0; Cl.yrows = 0;
-    Cl.park = nullptr; Cl.park_rows = 0;
-#else
     // The packed multipliers of the PGS solve are read m times per row update: they live in LDS whenever
     // that is free, i.e. in the Runge-Kutta stage rows, which only `runge_kutta_4` steps use (the shipped
-    // robots integrate with `euler_explicit`); otherwise in the workspace rows (HBM).
+    // robots integrate with `euler_explicit`); otherwise in the workspace rows (HBM).  (A block-local LDS array of
+    // their own made the solve faster, but the extra 14 kB per block cost one resident wave per CU: measured slower on
+    // warm-started workloads)
     constexpr bool fits = ConRows<Tp>::NR <= stage_rows<Tp>();
     const bool stage_rows_free = A.mode != MODE_STEP || A.solver != JM_SOLVER_RUNGE_KUTTA_4;
     Cl.yl = nullptr; Cl.ystride = 0; Cl.yrows = 0;
     Cl.park = nullptr; Cl.park_rows = 0;
-    if (JM_CON_XALIAS && fits)
+    if (fits)
     {
         if (!stage_rows_free)
         {
@@ -1581,7 +1433,6 @@ __global__ void __launch_bounds__(64) k_constrained(const BatchArgs<T> A, const 
         Cl.xl = C.ws + (size_t)ConRows<Tp>::WX * A.B + lane;
         Cl.xstride = (int)A.B;
     }
-#endif
     lane_run<T, Tp, 64, typename std::conditional<VAR, WithConA, WithCon>::type>(A, lane, lds + threadIdx.x, Cl);
 }
 #endif

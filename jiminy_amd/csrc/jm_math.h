@@ -35,22 +35,16 @@
 // soon as the kernel is built for two waves per SIMD (256 VGPRs).
 #define JM_KZ(dep) jm::kzero_(dep)
 #define JM_K(c, kz) __hiloint2double((int)(__builtin_bit_cast(unsigned long long, (double)(c)) >> 32) | (kz), (int)__builtin_bit_cast(unsigned long long, (double)(c)) | (kz))
-#ifndef JM_NO_REFRESH
 #define JM_REFRESH() asm volatile("" ::: "memory")
-#else
-#define JM_REFRESH() ((void)0)
-#endif
 #endif
 
 namespace jm
 {
-#ifndef JM_FP_REASSOC
-#define JM_FP_REASSOC 1   // (0: A/B builds; measured in round 4, same box: ANYmal launch 0.1517 -> 0.1480 ms, Atlas 0.3606 -> 0.3477)
-#endif
-#if JM_FP_REASSOC && !defined(JM_HOST_EMU)
+#ifndef JM_HOST_EMU
 // The spatial-algebra helpers below (and only they: the pragma is switched off again in front of the scalar functions, whose
 // Cody-Waite reductions and polynomials depend on their order of operations): a sum of products may be re-associated into one
-// fma chain, `a + (x y + z w + u v)` -> three fmas instead of mul + 2 fma + add
+// fma chain, `a + (x y + z w + u v)` -> three fmas instead of mul + 2 fma + add (measured in round 4,
+// same box: ANYmal launch 0.1517 -> 0.1480 ms, Atlas 0.3606 -> 0.3477)
 #pragma clang fp reassociate(on)
 #endif
 #ifndef JM_HOST_EMU
@@ -184,11 +178,6 @@ template<class T> struct Sp  // spatial motion or force, [linear; angular]
 template<class T> JM_DEV Sp<T> zero6() { return {zero3<T>(), zero3<T>()}; }
 template<class T> JM_DEV Sp<T> operator+(Sp<T> a, Sp<T> b) { return {a.l + b.l, a.a + b.a}; }
 template<class T> JM_DEV Sp<T> operator-(Sp<T> a, Sp<T> b) { return {a.l - b.l, a.a - b.a}; }
-template<class T> JM_DEV Sp<T> act_motion(const SE3<T> & M, Sp<T> m)
-{
-    const V3<T> Rw = M.R * m.a;
-    return {M.R * m.l + cross(M.p, Rw), Rw};
-}
 template<class T> JM_DEV Sp<T> actinv_motion(const SE3<T> & M, Sp<T> m)
 {
     return {tmul(M.R, m.l - cross(M.p, m.a)), tmul(M.R, m.a)};
@@ -308,7 +297,7 @@ template<class T> JM_DEV M3<T> quat_to_matrix(T x, T y, T z, T w)
             txz - twy, tyz + twx, T(1) - (txx + tyy)};
 }
 
-#if JM_FP_REASSOC && !defined(JM_HOST_EMU)
+#ifndef JM_HOST_EMU
 #pragma clang fp reassociate(off)
 #endif
 // sin and cos of a float64 angle without the libm `sincos(x, &s, &c)` out-pointer form: on the

@@ -41,33 +41,9 @@
 #include "jm_quad.h"
 #include "jm_constraint.h"
 
-#ifndef JM_QCON_SKIP
-#define JM_QCON_SKIP 0   // profiling only: bit 0 skip the PGS sweeps, 1 the delassus rounds, 2 the closing evaluation
-#endif
-#ifndef JM_QCON_PGS_INCR
-#define JM_QCON_PGS_INCR 1  // register-resident PGS: 1 = residuals maintained incrementally (y -= A[:, i] dx after every update,
-                            // no dot products and no quad reductions inside the sweeps), 0 = residual of a row = b - A x at its turn
-#endif
-#ifndef JM_QCON_PGS_FIXED
-#define JM_QCON_PGS_FIXED 1 // waves whose robots all fit the fixed row layout of qcon_pgs_fixed take it
-#endif
-#ifndef JM_QCON_DELTA
-#define JM_QCON_DELTA 0  // 1: evaluations that emit nothing apply the multipliers with one bias-free solve instead of the closing
-                         // full evaluation (cheaper arithmetic, but it keeps the free evaluation's data live across the PGS
-                         // sweeps: measured slower on ANYmal because the sweeps then spill)
-#endif
-#ifndef JM_QCON_INIT_ON_CHIP
-#define JM_QCON_INIT_ON_CHIP 1  // Engine::start / reset passes whose solve fits the on-chip part of the region take the branch-free
-                                // on-chip store and the register-resident sweeps like every other evaluation (0: round-5 behaviour,
-                                // the general store with its per-access LDS / HBM branch and the quad-cooperative sweeps: ANYmal,
-                                // 65 536 robots, reset of every lane 11.6 ms -- twelve times a step)
-#endif
 #ifndef JM_QCON_REGS_NIT
 #define JM_QCON_REGS_NIT 4  // on-chip solves of up to 4 * JM_QCON_REGS_NIT rows run out of registers (qcon_pgs_regs / _fixed), larger
                             // ones out of LDS (qcon_pgs with the on-chip store): a quarter of a 40-row matrix is 400 registers
-#endif
-#ifndef JM_QCON_WS_TILED
-#define JM_QCON_WS_TILED 1  // workspace rows tiled per wave (qcon_store)
 #endif
 #ifndef JM_QCON_PGS_WAVES
 #define JM_QCON_PGS_WAVES 2  // waves per SIMD of the split form's solve kernel (k_qcon_pgs)
@@ -216,20 +192,13 @@ template<class Tp> struct QSplitRegion
     static constexpr int HDR = 4 * MAXM + MAXM * MAXM + 32, OK = HDR + 1, LOCK = HDR + 2, ROWS = (LOCK + 2) & ~1;   // (even: 16-byte aligned regions)
 };
 
-// which topologies step in the split form (jm_qcon.h, bottom): solves of more than 32 rows
-// (JM_QCON_SPLIT_MIN: experimental builds -- codegen.qcon_split_min -- move the threshold, e.g. to put ANYmal's 28-row solves
-// through the split form: measured in round 5)
-#ifndef JM_QCON_SPLIT_MIN
-#define JM_QCON_SPLIT_MIN 32
-#endif
-#ifndef JM_QCON_PGS_LANE
-#define JM_QCON_PGS_LANE 1   // round 6: robots with few contact points step in the split form too, their solve one lane per robot (qcon_pgs_lane)
-#endif
+// which topologies step in the split form (jm_qcon.h, bottom): solves of more than 32 rows (codegen.qcon_split states the
+// same threshold; ANYmal's 28-row solves through the large split form were measured in round 5)
 // robots whose solves are LARGE (the streamed / operational-space forms; `start` / `reset` through the split kernels as well)
-template<class Tp> constexpr bool qcon_split_large() { return Tp::QUAD && QConRows<Tp>::MAXM > JM_QCON_SPLIT_MIN; }
-// robots whose whole solve fits the fixed 16-row layout of qcon_pgs_lane (up to five contact points): pre | solve | post as
+template<class Tp> constexpr bool qcon_split_large() { return Tp::QUAD && QConRows<Tp>::MAXM > 32; }
+// round 6: robots whose whole solve fits the fixed 16-row layout of qcon_pgs_lane (up to five contact points): pre | solve | post as
 // well -- the solve kernel holds a robot per lane, which the single kernel cannot (ANYmal: 0.87 -> 0.72-0.84 ms per launch)
-template<class Tp> constexpr bool qcon_split_lane() { return JM_QCON_PGS_LANE != 0 && Tp::QUAD && ConRows<Tp>::NC >= 1 && 3 * ConRows<Tp>::NC <= 16; }
+template<class Tp> constexpr bool qcon_split_lane() { return Tp::QUAD && ConRows<Tp>::NC >= 1 && 3 * ConRows<Tp>::NC <= 16; }
 template<class Tp> constexpr bool qcon_split() { return qcon_split_large<Tp>() || qcon_split_lane<Tp>(); }
 // which kernels know user-registered JointConstraints (bit 2 of a joint row's flag): the variation kernels, and every
 // constraint kernel of the topologies that step in the split form (their solves run out of the workspace anyway); the plain
@@ -988,12 +957,12 @@ JM_DEV bool qcon_pgs_regs(const QConArgs<T> & C, T friction, int k, const QConCt
     });
     const bool contacts_only = !X::wave_any(!(nb == 0 && cb == 3));
     bool converged = false;
-#if JM_QCON_PGS_INCR
     // Residual-maintaining form: y = b - A x is kept up to date for this lane's rows (i = k mod 4): a row update
     // x_i += dx costs the lane NIT multiply-adds on its rows (column i of A = row i, the matrix is symmetric) instead
     // of a dot product + quad butterfly per row.  At its turn the owner lane broadcasts y_i; the projection and the
     // stagnation bookkeeping (|y_i - y_i of the previous sweep|, |y_i|: constraint_solvers.cc:263-278) then run
-    // replicated in the four lanes.  Same iterates as the dot-product form up to the rounding of the running sums.
+    // replicated in the four lanes.  Same iterates as the dot-product form (residual of a row = b - A x at its turn) up to
+    // the rounding of the running sums; no dot products and no quad reductions inside the sweeps.
     T yturn[MR];   // residual of every row at its turn in the previous sweep (zero until a row is touched)
     static_for<0, MR>([&](auto ic) { yturn[decltype(ic)::value] = T(0); });
     static_for<0, MR>([&](auto ic) {
@@ -1030,111 +999,6 @@ JM_DEV bool qcon_pgs_regs(const QConArgs<T> & C, T friction, int k, const QConCt
             const T dx = val - x[i];
             x[i] = val;
             static_for<0, NIT>([&](auto jc) { yq[decltype(jc)::value] -= Aq[i][decltype(jc)::value] * dx; });
-        };
-        auto cone = [&](auto ic) __attribute__((always_inline)) {
-            constexpr int i = decltype(ic)::value;
-            if (friction_zero)
-            {
-                set_x(ic, x[i] * T(0));
-                set_x(std::integral_constant<int, i + 1>{}, x[i + 1] * T(0));
-            }
-            else
-            {
-                const T y0 = residual(ic);
-                const T y1 = residual(std::integral_constant<int, i + 1>{});
-                const T ia = fmin_(invd[i], invd[i + 1]);   // 1 / max(a00, a11)
-                T e0 = x[i] + (w * y0) * ia;
-                T e1 = x[i + 1] + (w * y1) * ia;
-                const T thr = friction * x[i + 2];
-                const T n2 = e0 * e0 + e1 * e1;
-                if (n2 > thr * thr)
-                {
-                    const T scale = thr / sqrt_(n2);
-                    e0 *= scale;
-                    e1 *= scale;
-                }
-                set_x(ic, e0);
-                set_x(std::integral_constant<int, i + 1>{}, e1);
-            }
-        };
-        if (contacts_only)
-        {
-            static_for<0, MR / 3>([&](auto jc) {
-                constexpr int i = 3 * decltype(jc)::value + 2;
-                if (i < m)
-                {
-                    const T yy = residual(std::integral_constant<int, i>{});
-                    set_x(std::integral_constant<int, i>{}, X::max_(x[i] + (w * yy) * invd[i], T(0)));
-                }
-            });
-            static_for<0, MR / 3>([&](auto jc) {
-                constexpr int i = 3 * decltype(jc)::value;
-                if (i + 2 < m) cone(std::integral_constant<int, i>{});
-            });
-        }
-        else
-        {
-        static_for<0, MR>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            if ((any0 >> i) & 1u)
-                if ((mask0 >> i) & 1u)
-                {
-                    const T yy = residual(ic);
-                    set_x(ic, X::max_(x[i] + (w * yy) * invd[i], T(0)));
-                }
-        });
-        static_for<1, MR>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            if ((any1 >> i) & 1u)
-            if ((mask1 >> i) & 1u)
-            {
-                if (torsion_zero) set_x(ic, x[i] * T(0));
-                else
-                {
-                    const T yy = residual(ic);
-                    const T thr = C.torsion * x[i - 1];
-                    set_x(ic, clamp_(x[i] + (w * yy) * invd[i], -thr, thr));
-                }
-            }
-        });
-        static_for<0, MR - 2>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            if ((any2 >> i) & 1u)
-                if ((mask2 >> i) & 1u) cone(ic);
-        });
-        }
-        // (every lane followed every row: dmax / ymax are already those of the robot)
-        const T tol = C.tol_abs + C.tol_rel * ymax + eps;
-        converged = dmax < tol;
-    }
-#else
-#pragma nounroll
-    for (unsigned iter = 0; iter < iter_max && !converged; ++iter)
-    {
-        T dmax = T(0), ymax = T(0);
-        const T ratio = (T(iter_max - 20u) - T(iter)) / T(iter_max - 20u - 30u);
-        T w = T(1);
-        if (ratio < T(1))
-        {
-            w = T(0.01);
-            if (ratio > T(0)) w += (T(1) - T(0.01)) * (ratio * ratio);
-        }
-        auto residual = [&](auto ic) __attribute__((always_inline)) {
-            constexpr int i = decltype(ic)::value;
-            T s = T(0);
-            static_for<0, NIT>([&](auto jc) { s += Aq[i][decltype(jc)::value] * xq[decltype(jc)::value]; });
-            // the owner lane of row i (i mod 4) holds b and the previous residual; its result goes to the quad
-            const T mine = bq[i >> 2] - X::quad_sum(s);
-            const bool own = k == (i & 3);
-            dmax = X::max_abs(dmax, own ? mine - yq[i >> 2] : T(0));
-            ymax = X::max_abs(ymax, own ? mine : T(0));
-            yq[i >> 2] = own ? mine : yq[i >> 2];
-            return X::template bcast<(i & 3)>(mine);
-        };
-        auto set_x = [&](auto ic, T val) __attribute__((always_inline)) {
-            constexpr int i = decltype(ic)::value;
-            x[i] = val;
-            if (k == (i & 3)) xq[i >> 2] = val;
         };
         auto cone = [&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
@@ -1213,13 +1077,10 @@ JM_DEV bool qcon_pgs_regs(const QConArgs<T> & C, T friction, int k, const QConCt
                 if ((mask2 >> i) & 1u) cone(ic);
         });
         }
-        // (dmax / ymax: every lane saw its own rows)
-        dmax = X::max_(dmax, X::template perm_<0xB1>(dmax)); dmax = X::max_(dmax, X::template perm_<0x4E>(dmax));
-        ymax = X::max_(ymax, X::template perm_<0xB1>(ymax)); ymax = X::max_(ymax, X::template perm_<0x4E>(ymax));
+        // (every lane followed every row: dmax / ymax are already those of the robot)
         const T tol = C.tol_abs + C.tol_rel * ymax + eps;
         converged = dmax < tol;
     }
-#endif
     // multipliers back to the region (qcon_scatter reads them from there)
     X::sync();
     if (lead)
@@ -1454,88 +1315,6 @@ JM_DEV bool qcon_chol(int k, int m, const VS & V)
     return X::quad_or(ok ? 0 : 1) == 0;
 }
 
-// ---------------------------------------------------------------- multipliers applied: a += M^-1 J^T lambda
-// One bias-free solve of the whole robot by the quad (evaluations that emit nothing: the closing full
-// evaluation with the constraint forces would cost four times as much): every lane pushes the constraint forces
-// of ITS limb (bound multipliers as joint efforts, contact multipliers as a wrench on the tip) down to the
-// attachment joint, the quad sums enter the trunk tree, and the accelerations come back up.
-template<class T, class Tp, class X, bool GND = false>
-JM_DEV void qcon_apply_delta(CPtr<T> P, const LimbTable<T> & LT, const QConArgs<T> & C, unsigned B32, unsigned r32, int k,
-                             const QIdx<Tp> & ix, const QKeep<T, Tp> & K, const TrunkStore<T, Tp> & TS, const QConCtx<T, Tp> & cx,
-                             T * ddqb, T * ddq, int & status)
-{
-    using Q = QLayout<Tp>;
-    using R = ConRows<Tp>;
-    using QR = QConRows<Tp>;
-    using I = QInfo<Tp>;
-    constexpr int N = Tp::QN, NT = Tp::QT;
-    auto lam = [&](int row) { return C.data[(unsigned)(R::LAM + row) * B32 + r32]; };
-    T tau_l[N], tau_b[NT];
-    static_for<0, N>([&](auto sc) {
-        constexpr int s = decltype(sc)::value;
-        const int row = sel4(k, QR::limb_row(0, s), QR::limb_row(1, s), QR::limb_row(2, s), QR::limb_row(3, s));
-        const bool on = row >= 0 && ix.has[s] && cx.act.test(row);
-        const T l = on ? lam(on ? row : 0) : T(0);
-        tau_l[s] = (on && cx.rev.test(row)) ? -l : l;
-    });
-    tau_b[0] = T(0);
-    static_for<1, NT>([&](auto tc) {
-        constexpr int t = decltype(tc)::value;
-        constexpr int row = QR::trunk_row(t);
-        tau_b[t] = T(0);
-        if constexpr (row >= 0)
-        {
-            const T l = cx.act.test(row) ? lam(row) : T(0);
-            tau_b[t] = cx.rev.test(row) ? -l : l;
-        }
-    });
-    Sp<T> ftip = zero6<T>();
-    auto contact = [&](int cl) {
-        if (cl >= ix.nc) return;
-        const int oc = Q::CONTACT + cl * Q::QC;
-        const int r0 = R::NB + 4 * (int)LT(oc + Q::C_IDX);
-        if (!cx.act.test(r0)) return;
-        const V3<T> pc = K.Rt * LT.v3(oc + 9) + K.ps[N - 1];
-        T dep_;
-        const M3<T> Mc = contact_frame<GND>(C, K.R1, K.p1, pc, dep_);
-        const V3<T> fR = tmul(Mc, V3<T>{lam(r0), lam(r0 + 1), lam(r0 + 2)});
-        ftip.l = ftip.l + fR;
-        ftip.a = ftip.a + cross(pc, fR);
-        if (cx.cb == 4) ftip.a = ftip.a + lam(r0 + 3) * V3<T>{Mc.m20, Mc.m21, Mc.m22};
-    };
-    if constexpr (Tp::QCL <= 2) static_for<0, Tp::QCL>([&](auto cc) { contact(decltype(cc)::value); });
-    else
-    {
-#pragma nounroll
-        for (int cl = 0; cl < Tp::QCL; ++cl) contact(cl);
-    }
-    T ul[N];
-    const Sp<T> fbase = limb_push<T, Tp>(K, tau_l, ftip, ul);
-    Sp<T> accF[NT];
-    static_for<0, NT>([&](auto tc) {
-        constexpr int t = decltype(tc)::value;
-        if constexpr (I::limb_at(t))
-        {
-            if constexpr (I::uniform_attach) accF[t] = quad_sum6<T, X>(fbase);
-            else accF[t] = quad_sum6<T, X>(mask6(ix.attach == t, fbase));
-        }
-        else accF[t] = zero6<T>();
-    });
-    Sp<T> at[NT];
-    T ddb[NT];
-    trunk_column<T, Tp, X>(P, K, TS, accF, tau_b, at, ddb);
-    T dd[N];
-    (void)limb_pull<T, Tp>(K, ix, ul, true, pick_attach<T, Tp>(k, at), dd);
-    bool bad = false;
-    ddqb[0] += at[0].l.x; ddqb[1] += at[0].l.y; ddqb[2] += at[0].l.z;
-    ddqb[3] += at[0].a.x; ddqb[4] += at[0].a.y; ddqb[5] += at[0].a.z;
-    static_for<1, NT>([&](auto tc) { ddqb[5 + decltype(tc)::value] += ddb[decltype(tc)::value]; });
-    static_for<0, N>([&](auto sc) { ddq[decltype(sc)::value] += dd[decltype(sc)::value]; });
-    static_for<0, I::NVB>([&](auto ic) { bad |= (ddqb[decltype(ic)::value] != ddqb[decltype(ic)::value]); });
-    static_for<0, N>([&](auto sc) { bad |= ix.has[decltype(sc)::value] && (ddq[decltype(sc)::value] != ddq[decltype(sc)::value]); });
-    if (bad) status |= JM_LANE_NAN;
-}
-
 }  // namespace jm
 #include "jm_qtip.h"
 namespace jm
@@ -1549,7 +1328,7 @@ namespace jm
 template<class T, class Tp, class X, class SB, int CAPC, bool GEN, int PH, int INIT>
 JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, const QConArgs<T> & C, const QStore<T> & V,
                           unsigned r, int k, const QIdx<Tp> & ix, const SB & S_, const T * qb, const T * vb, const T * ql,
-                          const T * vl, const T * cmdb, const T * cmdl, bool emit, bool sensors, T * ddqb, T * ddq, int & status,
+                          const T * vl, bool emit, bool sensors, T * ddqb, T * ddq, int & status,
                           int start_passes, T te)
 {
     using L = Layout<Tp>;
@@ -1568,8 +1347,8 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
     ex.nb = R::NB;
     status &= ~JM_LANE_SOLVER_FAILURE;
     auto apply = [&]() __attribute__((always_inline)) {
-        if (emit) quad_eval<T, Tp, X, true, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, sensors, ddqb, ddq, status, &ex, nullptr, nullptr, te);
-        else quad_eval<T, Tp, X, false, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status, &ex, nullptr, nullptr, te);
+        if (emit) quad_eval<T, Tp, X, true, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, sensors, ddqb, ddq, status, &ex, nullptr, nullptr, te);
+        else quad_eval<T, Tp, X, false, SB, 2, NoKeep, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, false, ddqb, ddq, status, &ex, nullptr, nullptr, te);
     };
     if constexpr (R::NR == 0)
     {
@@ -1646,7 +1425,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
                 static_for<0, N>([&](auto sc) { ex.tau_l[decltype(sc)::value] = uq_l[decltype(sc)::value]; });
                 static_for<0, NT>([&](auto tc) { ex.tau_b[decltype(tc)::value] = uq_b[decltype(tc)::value]; });
                 ex.motors_on = true;
-                quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq,
+                quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, false, ddqb, ddq,
                                                                status, &ex, &K, &TS, te);
                 if (any)
                 {
@@ -1658,7 +1437,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
                 return;
             }
             ex.motors_on = !init;   // (first pass of Engine::start: RobotState::u is still zero)
-            quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq,
+            quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, false, ddqb, ddq,
                                                            status, &ex, &K, &TS, te);
             qcon_switch<T, Tp, X, GEN>(P, LT, C, B32, r32, k, ix, qb, ql, K, init, false, cx);
             any = cx.act.any();
@@ -1727,7 +1506,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
         static_for<0, N>([&](auto sc) { ex.tau_l[decltype(sc)::value] = uq_l[decltype(sc)::value]; });
         static_for<0, NT>([&](auto tc) { ex.tau_b[decltype(tc)::value] = uq_b[decltype(tc)::value]; });
         ex.motors_on = !(init && pass == 0);
-        quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq,
+        quad_eval<T, Tp, X, false, SB, 1, QKeep<T, Tp>, GEN>(P, LT, A, r32, k, ix, S_, qb, vb, ql, vl, false, ddqb, ddq,
                                                        status, &ex, &K, &TS, te);
         if (pass == 0)
         {
@@ -1739,7 +1518,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
         // delassus matrix (first pass), right-hand side and warm start, solve, multipliers back to the lane state
         auto phases = [&](const auto & W) __attribute__((always_inline)) {
             using VS = std::decay_t<decltype(W)>;
-            if (pass == 0 && !(JM_QCON_SKIP & 2)) qcon_delassus<T, Tp, X, VS, GEN>(P, LT, C, k, ix, K, TS, cx, W);
+            if (pass == 0) qcon_delassus<T, Tp, X, VS, GEN>(P, LT, C, k, ix, K, TS, cx, W);
             X::sync();
             qcon_rhs<T, Tp, VS, GEN>(P, LT, C, B32, r32, k, ix, qb, vb, ql, vl, ddqb, ddq, K, cx, W);
             X::sync();
@@ -1760,11 +1539,12 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
                     // (robots with user-registered JointConstraints: the general form knows the unbounded rows)
                     bool general = false;
                     if constexpr (qcon_locks<Tp, GEN>()) general = X::wave_any(cx.lockp != 0ull);
-                    if (general) { if (!(JM_QCON_SKIP & 1)) ok = qcon_pgs<T, Tp, X, VS>(C, friction, k, cx, W); }
-                    else if (!(JM_QCON_SKIP & 1))
+                    if (general) ok = qcon_pgs<T, Tp, X, VS>(C, friction, k, cx, W);
+                    else
                     {
                         bool fixed = false;
-                        if constexpr (JM_QCON_PGS_FIXED && 3 * ConRows<Tp>::NC <= 4 * VS::NIT)
+                        // waves whose robots all fit the fixed row layout of qcon_pgs_fixed take it
+                        if constexpr (3 * ConRows<Tp>::NC <= 4 * VS::NIT)
                         {
                             fixed = !X::wave_any(cx.cb != 3 || cx.nb > 4 * VS::NIT - 3 * ConRows<Tp>::NC || friction < Eps<T>::eps);
                             if (fixed) ok = qcon_pgs_fixed<T, Tp, X, VS::NIT>(C, friction, k, cx, W.lds);
@@ -1772,7 +1552,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
                         if (!fixed) ok = qcon_pgs_regs<T, Tp, X, VS::NIT>(C, friction, k, cx, W.lds);
                     }
                 }
-                else if (!(JM_QCON_SKIP & 1)) ok = qcon_pgs<T, Tp, X, VS>(C, friction, k, cx, W);
+                else ok = qcon_pgs<T, Tp, X, VS>(C, friction, k, cx, W);
                 if (ok) status &= ~JM_LANE_SOLVER_FAILURE;
                 else status |= JM_LANE_SOLVER_FAILURE;
                 if (cx.overflow) status |= JM_LANE_SOLVER_FAILURE;
@@ -1783,8 +1563,11 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
         constexpr int MFIT = QR::mfit(CAPC);
         if constexpr (MFIT >= 4)
         {
-            // the whole solve of this robot fits the on-chip part of its region (quad-uniform decision)
-            if ((JM_QCON_INIT_ON_CHIP || !init) && cx.m <= MFIT) phases(QStoreChip<T, (MFIT + 3) / 4>{V.lds});
+            // the whole solve of this robot fits the on-chip part of its region (quad-uniform decision).  Engine::start / reset
+            // passes take the branch-free on-chip store and the register-resident sweeps like every other evaluation (round 5
+            // sent them through the general store with its per-access LDS / HBM branch and the quad-cooperative sweeps: ANYmal,
+            // 65 536 robots, reset of every lane 11.6 ms -- twelve times a step)
+            if (cx.m <= MFIT) phases(QStoreChip<T, (MFIT + 3) / 4>{V.lds});
             else phases(V);
         }
         else phases(V);
@@ -1806,13 +1589,9 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
     }
     // ---- nothing to enforce and nothing to emit: the free acceleration is the answer (engine.cc:3861-3865)
     if (PH == 0 && !emit && !any && !init) return;
-    if (JM_QCON_DELTA && !emit && !init && !refresh && !(JM_QCON_SKIP & 4))
-    {
-        // nothing to emit: the free acceleration plus one bias-free solve with the multipliers
-        qcon_apply_delta<T, Tp, X, GEN>(P, LT, C, B32, r32, k, ix, K, TS, cx, ddqb, ddq, status);
-        return;
-    }
     // ---- apply the multipliers: articulated-body solve with the constraint forces; emits the outputs
+    // (evaluations that emit nothing take it too: one bias-free solve with the multipliers instead is cheaper arithmetic, but
+    // it keeps the free evaluation's data live across the PGS sweeps -- measured slower on ANYmal because the sweeps then spill)
     static_for<0, N>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
         const int row = sel4(k, QR::limb_row(0, s), QR::limb_row(1, s), QR::limb_row(2, s), QR::limb_row(3, s));
@@ -1834,7 +1613,7 @@ JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T>
         else { ex.tau_b[t] = uq_b[t]; ex.uemit_b[t] = T(0); }
     });
     ex.motors_on = true;
-    if (!(JM_QCON_SKIP & 4)) apply();
+    apply();
 }
 
 // Visit table of one Gauss-Seidel sweep over the m packed rows of a solve (`nb` joint rows, then blocks of `cb` rows per
@@ -2304,9 +2083,6 @@ template<class T, class Tp> constexpr long qcon_free_lds(int wr, int wb)
 }
 template<class T, class Tp> constexpr int qcon_resident_waves()
 {
-#ifdef JM_QCON_RESIDENT_WAVES
-    return JM_QCON_RESIDENT_WAVES;   // tuning override
-#endif
     for (int wr = 4; wr > 1; wr /= 2)
     {
         const int wb = wr < quad_block_waves<T, Tp>() ? wr : quad_block_waves<T, Tp>();
@@ -2337,10 +2113,8 @@ template<class T, class Tp> constexpr int qcon_ws_rows() { return QConRows<Tp>::
 template<class T, class Tp> JM_DEV QStore<T> qcon_store(T * lds, T * ws, long long r, unsigned B)
 {
     constexpr int CAP = qcon_capacity<T, Tp>();
-#if JM_QCON_WS_TILED
     if ((B & 15u) == 0)
         return {lds, ws + (size_t)(r >> 4) * (size_t)(qcon_ws_rows<T, Tp>() * 16) + (size_t)(r & 15), 16u, CAP};
-#endif
     return {lds, ws + r, B, CAP};
 }
 

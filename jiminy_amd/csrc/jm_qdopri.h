@@ -69,11 +69,8 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
     });
     cmdb[0] = T(0);
     static_for<1, NT>([&](auto tc) { cmdb[decltype(tc)::value] = A.command[(unsigned)Tp::trunk_motor[decltype(tc)::value] * B32 + r32]; });
-    if constexpr (R::CMD_LDS)
-    {
-        static_for<0, N>([&](auto sc) { S.putl(R::CMDL + decltype(sc)::value, cmdl[decltype(sc)::value]); });
-        static_for<0, NT>([&](auto tc) { S.putb(R::CMDB + decltype(tc)::value, cmdb[decltype(tc)::value]); });
-    }
+    static_for<0, N>([&](auto sc) { S.putl(R::CMDL + decltype(sc)::value, cmdl[decltype(sc)::value]); });
+    static_for<0, NT>([&](auto tc) { S.putb(R::CMDB + decltype(tc)::value, cmdb[decltype(tc)::value]); });
     // x0 = (q, v), k_0 = (v, a) into the stage buffer
     static_for<0, NQB>([&](auto ic) { S.putb(R::Q0B + decltype(ic)::value, A.q[(unsigned)I::qrow(decltype(ic)::value) * B32 + r32]); });
     static_for<0, NVB>([&](auto ic) {
@@ -200,14 +197,11 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
                 int evst = 0;
                 T te = T(0);
                 if constexpr (GEN) te = (T)dopri::stage_time(tl, i, dt);
-                quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, r32, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, evst,
+                quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, r32, k, ix, S, qb, vb, ql, vl, false, ddqb, ddq, evst,
                                                                                 nullptr, nullptr, nullptr, te);
                 static_for<0, NVB>([&](auto ic) { S.putb(DR::KAB + (i - 1) * NVB + decltype(ic)::value, ddqb[decltype(ic)::value]); });
                 static_for<0, N>([&](auto sc) { if (ix.has[decltype(sc)::value]) kal[krow(i, decltype(sc)::value)] = ddq[decltype(sc)::value]; });
             }
-#ifdef JM_DOPRI_BARRIER   // (experiment of DESIGN.md section 4.7: nothing of the stage loop is carried into the estimate in registers)
-            JM_REFRESH();
-#endif
             // ---- embedded error estimate (runge_kutta_dopri_stepper.cc:18-87): solution = stage 6 = (qb|ql, vb|vl),
             // alternative (4th order) solution = x0 (+) dt sum_j e_j k_j, norm = max |difference / scale|
             double error = 0.0;
@@ -274,16 +268,6 @@ JM_DEV void quad_dopri_run(const BatchArgs<T> & A, const AdaptiveArgs<T> & D, lo
                 nan |= (eq != eq) || (ev != ev);
                 error = fmax(error, fmax(eq, ev));
                 a_nan |= (ddq[s] != ddq[s]);
-#ifdef JM_DOPRI_DEBUG   // (the terms of the first attempt's estimate, into rows the persistent kernel does not use)
-#ifndef JM_DOPRI_DEBUG_ATT
-#define JM_DOPRI_DEBUG_ATT 1
-#endif
-                if (attempts == JM_DOPRI_DEBUG_ATT && ix.has[s])
-                {
-                    D.ws[(unsigned long long)(AR::QS + ix.rq[s]) * Bq + r32] = JM_DOPRI_DEBUG == 1 ? (q0 + dq) - ql[s] : (JM_DOPRI_DEBUG == 2 ? ql[s] : q0 + dq);
-                    D.ws[(unsigned long long)(AR::CMD + ix.rm[s]) * Bq + r32] = JM_DOPRI_DEBUG == 1 ? (v0 + dv) - vl[s] : (JM_DOPRI_DEBUG == 2 ? vl[s] : v0 + dv);
-                }
-#endif
             });
             {
                 // over the four limbs (fmax drops NaN operands: the flags travel separately)

@@ -24,9 +24,6 @@
 // rows; the others keep the streamed form.  Included by jm_qcon.h.
 #pragma once
 
-#ifndef JM_QTIP
-#define JM_QTIP 1            // 0: never take the operational-space form (A / B runs)
-#endif
 #ifndef JM_QTIP_WAVES
 #define JM_QTIP_WAVES 1      // waves per SIMD of k_qtip_pgs (measured, Atlas B = 32 768: 2.40 ms per solve at 1, 2.66 at 2 -- issue-bound either way)
 #endif
@@ -58,7 +55,7 @@ template<class Tp> struct QTip
                                                   // (Atlas standing in its neutral pose already has five joints at a limit)
     static constexpr int NE = 6 * NCT + NBX;      // extended operational space
     static constexpr int ZL = (NE + 3) / 4;       // entries of z / rows of E per lane (entry e: lane e & 3, slot e >> 2)
-    static constexpr bool ON = JM_QTIP != 0 && qcon_split_large<Tp>() && NCT >= 1 && NCT <= 2;
+    static constexpr bool ON = qcon_split_large<Tp>() && NCT >= 1 && NCT <= 2;
     // the robot's region of the workspace in this form: x | b | y | 1 / diag (4 m, as in every form: what qcon_rhs / qcon_scatter
     // read and write) | E (NE x NE, row-major) | one record of REC scalars per row, everything a row visit reads in one
     // 96-byte block: X[6] | b | 1 / diag | R | y of the previous sweep | z offset (as an integer in the scalar's low word) | -

@@ -199,16 +199,11 @@ template<class Tp> struct QRows
     static constexpr int Q0L = 0, V0L = N, ACCVL = 2 * N, ACCAL = 3 * N, KVL = 4 * N;  // limb rows
     // Long limbs (register-bound kernels): the evaluation re-reads the stage velocity (= the kv rows)
     // and the held commands from LDS where it needs them instead of keeping them live in VGPRs.
-#ifdef JM_QUAD_LEAN
-    static constexpr bool LONG = true;   // tuning: register-lean variant regardless of the limb length
-#else
     static constexpr bool LONG = N > 4;
-#endif
     // The held commands always live in the stage buffer: in registers they are three to seven loop-invariant
     // pairs per lane that the two-waves-per-SIMD build (256 VGPRs) spills to scratch.
-    static constexpr bool CMD_LDS = true;
-    static constexpr int CMDL = 5 * N, NL = CMD_LDS ? 6 * N : 5 * N;
-    static constexpr int CMDB = KVB + NVB, NB = CMD_LDS ? CMDB + Tp::QT : CMDB;
+    static constexpr int CMDL = 5 * N, NL = 6 * N;
+    static constexpr int CMDB = KVB + NVB, NB = CMDB + Tp::QT;
 };
 
 // Split constrained stepping (jm_qcon.h: one evaluation = three launches, pre | solve | post): the stage buffer lives in
@@ -745,7 +740,8 @@ template<class T, class Tp> struct QKeep
 
 // a = f(q, v) for one robot spread over a quad; lane k evaluates limb k.
 //   qb[NQB], vb[NVB] : trunk-tree configuration / velocity (identical in the 4 lanes)
-//   ql[N], vl[N], cmdl[N] : this limb's joints;  cmdb[NT] : commands of the trunk-tree motors
+//   ql[N], vl[N] : this limb's joints;  the held commands of its motors and of the trunk-tree motors are read from the
+//   stage buffer (QRows::CMDL / CMDB)
 // When EMIT is set -- last evaluation of a step, `start`, `reset` -- the outputs that
 // derive from this evaluation (RobotState::u / uMotor / fExternal, contact forces, energies and,
 // if `sensors`, the sensor rows) are written right where their inputs are live, so that nothing
@@ -756,7 +752,7 @@ template<class T, class Tp> struct QKeep
 // everywhere (two waves per SIMD), and the outputs cost about a third of an evaluation once per launch.
 template<class T, class Tp, class X, bool EMIT, class SB, int CFM = 0, class KEEP = NoKeep, bool GEN = false, bool DYN = true>
 JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, unsigned r, int k, const QIdx<Tp> & ix,
-                      const SB & S_, const T * qb, const T * vb_, const T * ql, const T * vl_, const T * cmdb_, const T * cmdl_,
+                      const SB & S_, const T * qb, const T * vb_, const T * ql, const T * vl_,
                       bool sensors, T * ddqb, T * ddq, int & status, const QExtra<T, Tp> * ex = nullptr, KEEP * keep = nullptr,
                       TrunkStore<T, Tp> * ts_out = nullptr, T te = T(0))
 {
@@ -765,8 +761,8 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
     using RW = QRows<Tp>;
     auto vlq = [&](int s) -> T { if constexpr (RW::LONG) return S_.getl(RW::KVL + s); else return vl_[s]; };
     auto vbq = [&](int i) -> T { if constexpr (RW::LONG) return S_.getb(RW::KVB + i); else return vb_[i]; };
-    auto cmdlq = [&](int s) -> T { if constexpr (RW::CMD_LDS) return S_.getl(RW::CMDL + s); else return cmdl_[s]; };
-    auto cmdbq = [&](int t) -> T { if constexpr (RW::CMD_LDS) return S_.getb(RW::CMDB + t); else return cmdb_[t]; };
+    auto cmdlq = [&](int s) -> T { return S_.getl(RW::CMDL + s); };
+    auto cmdbq = [&](int t) -> T { return S_.getb(RW::CMDB + t); };
     // compile-time: the three non-emitting evaluations of an RK4 step carry no output code at all,
     // which keeps their basic blocks large (LDS reads of the limb table get batched ahead of use)
     constexpr bool emit = EMIT;
@@ -845,12 +841,8 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
     (void)limb_joint_of;
     trunk_fk_store<T, Tp, X, MA>(P, k, ix, qb, vb_, TS, Xatt, vatt, status, ma);
     // ---- limb kinematics (long limbs: cos / sin per joint + the tip placement only, see limb_fk_tip)
-#ifdef JM_OUTPUT_KEEP_KIN
-    constexpr bool UNWIND = QRows<Tp>::LONG;
-#else
     // (the output pass always takes the register-lean form: its sweep carries the momentum / wrench accumulators instead)
     constexpr bool UNWIND = QRows<Tp>::LONG || !DYN;
-#endif
     constexpr bool REWIND = UNWIND;   // ... and the forward sweep re-derives joint origins / axes (limb_rewind)
     M3<T> Rs[UNWIND ? 1 : N];
     V3<T> ps[N];
@@ -1751,7 +1743,7 @@ template<class Tp> struct QSplitRegion;   // (jm_qcon.h)
 template<class T, class Tp, class X, class SB, int CAPC, bool GEN, int PH = 0, int INIT = -1>
 JM_DEV void quad_eval_con(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A, const QConArgs<T> & C, const QStore<T> & V,
                           unsigned r, int k, const QIdx<Tp> & ix, const SB & S_, const T * qb, const T * vb, const T * ql,
-                          const T * vl, const T * cmdb, const T * cmdl, bool emit, bool sensors, T * ddqb, T * ddq, int & status,
+                          const T * vl, bool emit, bool sensors, T * ddqb, T * ddq, int & status,
                           int start_passes, T te = T(0));
 
 // one lane of a quad: robot r, limb k. `S` = stage buffer views of this lane.  QCON: every evaluation is the
@@ -1783,11 +1775,8 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
     });
     cmdb[0] = T(0);
     static_for<1, NT>([&](auto tc) { cmdb[decltype(tc)::value] = A.command[(unsigned)Tp::trunk_motor[decltype(tc)::value] * B32 + r32]; });
-    if constexpr (R::CMD_LDS)
-    {
-        static_for<0, N>([&](auto sc) { S.putl(R::CMDL + decltype(sc)::value, cmdl[decltype(sc)::value]); });
-        static_for<0, NT>([&](auto tc) { S.putb(R::CMDB + decltype(tc)::value, cmdb[decltype(tc)::value]); });
-    }
+    static_for<0, N>([&](auto sc) { S.putl(R::CMDL + decltype(sc)::value, cmdl[decltype(sc)::value]); });
+    static_for<0, NT>([&](auto tc) { S.putb(R::CMDB + decltype(tc)::value, cmdb[decltype(tc)::value]); });
 
     // every mode runs through the same evaluation loop (two inlined copies of the dynamics: with
     // and without the output code): `start`, `reset` and `dynamics` are one evaluation at a given
@@ -2021,7 +2010,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
                 });
             }
             // (start / reset in the split form: the four passes of Engine::start are launches of their own, C->split_pass)
-            quad_eval_con<T, Tp, X, StageBuf<T, SL, SB>, CAPC, GEN, PH, INIT>(P, LT, A, *C, *V, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, last,
+            quad_eval_con<T, Tp, X, StageBuf<T, SL, SB>, CAPC, GEN, PH, INIT>(P, LT, A, *C, *V, rr, k, ix, S, qb, vb, ql, vl, last,
                                     !stepping || A.update_sensors != 0, ddqb, ddq, status,
                                     INIT == 1 ? 4 : (INIT == 0 ? 0 : ((A.mode == MODE_START || A.mode == MODE_RESET) ? 4 : 0)));
             if (PH == 1 || !last)
@@ -2047,7 +2036,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
             JM_OPAQUE(rr);
             advance(st, last, rr);
             if (stepping) stage_time(st);
-            quad_eval_con<T, Tp, X, StageBuf<T, SL, SB>, CAPC, GEN, 0, INIT>(P, LT, A, *C, *V, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, last && A.mode != MODE_DYNAMICS,
+            quad_eval_con<T, Tp, X, StageBuf<T, SL, SB>, CAPC, GEN, 0, INIT>(P, LT, A, *C, *V, rr, k, ix, S, qb, vb, ql, vl, last && A.mode != MODE_DYNAMICS,
                                     (!stepping && A.mode != MODE_REFRESH) || A.update_sensors != 0, ddqb, ddq, status,
                                     start_passes, te);
         }
@@ -2077,7 +2066,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
             if constexpr (R::LONG && !GEN) JM_OPAQUE_S(Pl);
             advance(st, e == n_evals - 1, rr);
             stage_time(st);
-            quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(Pl, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status,
+            quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(Pl, LT, A, rr, k, ix, S, qb, vb, ql, vl, false, ddqb, ddq, status,
                                                                              nullptr, nullptr, nullptr, te);
         }
     }
@@ -2087,7 +2076,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         rr = r32;
         JM_OPAQUE(rr);
         advance(-1, true, rr);
-        quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl, false, ddqb, ddq, status,
+        quad_eval<T, Tp, X, false, StageBuf<T, SL, SB>, 0, NoKeep, GEN>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl, false, ddqb, ddq, status,
                                                                          nullptr, nullptr, nullptr, te);
     }
     if (A.mode != MODE_DYNAMICS)
@@ -2100,7 +2089,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         static_for<0, NQB>([&](auto ic) { qb[decltype(ic)::value] = S.getb(R::Q0B + decltype(ic)::value); });
         static_for<0, NVB>([&](auto ic) { vb[decltype(ic)::value] = S.getb(R::V0B + decltype(ic)::value); });
         static_for<0, N>([&](auto sc) { ql[decltype(sc)::value] = S.getl(R::Q0L + decltype(sc)::value); vl[decltype(sc)::value] = S.getl(R::V0L + decltype(sc)::value); });
-        quad_eval<T, Tp, X, true, StageBuf<T, SL, SB>, 0, NoKeep, GEN, false>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl, cmdb, cmdl,
+        quad_eval<T, Tp, X, true, StageBuf<T, SL, SB>, 0, NoKeep, GEN, false>(P, LT, A, rr, k, ix, S, qb, vb, ql, vl,
                                   (!stepping && A.mode != MODE_REFRESH) || A.update_sensors != 0, ddqb, ddq, status,
                                   nullptr, nullptr, nullptr, te);
     }
@@ -2179,11 +2168,7 @@ struct DppQuad
     }
     static __device__ __forceinline__ float max_abs(float a, float b) { return fmaxf(a, fabsf(b)); }
     static __device__ __forceinline__ float max_(float a, float b) { return fmaxf(a, b); }
-#ifdef JM_SYNC_FENCE   // (experiment of DESIGN.md section 4.7: the quad's hand-over points as compiler-visible memory fences)
-    static __device__ __forceinline__ void sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-#else
     static __device__ __forceinline__ void sync() {}  // lanes of a wave are already in lock-step
-#endif
     // stores of the quad's lanes to the workspace become visible to the other lanes' later loads
     static __device__ __forceinline__ void fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
     static __device__ __forceinline__ void table_ready() { __syncthreads(); }
@@ -2193,9 +2178,6 @@ struct DppQuad
 // waves resident per CU under the 160 KiB of LDS (a CU runs at most 2 such waves per SIMD).
 template<class T, class Tp> constexpr int quad_block_waves()
 {
-#ifdef JM_QUAD_BLOCK_WAVES
-    return JM_QUAD_BLOCK_WAVES;   // tuning override
-#endif
     constexpr long per_wave = (long)sizeof(T) * (QRows<Tp>::NL * 64 + QRows<Tp>::NB * 16);
     constexpr long table = (long)sizeof(T) * QLayout<Tp>::TABLE;
     int best = 1, best_resident = 0;
@@ -2216,9 +2198,6 @@ template<class T, class Tp> constexpr int quad_block_waves()
 // The per-environment variation kernels (GEN) and robots with a trunk tree spill at 256 registers: one wave.
 template<class T, class Tp, int W, bool GEN = false> constexpr int quad_waves_per_eu()
 {
-#ifdef JM_QUAD_WAVES_PER_EU
-    return JM_QUAD_WAVES_PER_EU;   // tuning override
-#endif
     constexpr long per_wave = (long)sizeof(T) * (QRows<Tp>::NL * 64 + QRows<Tp>::NB * 16);
     constexpr long block = (long)sizeof(T) * QLayout<Tp>::TABLE + W * per_wave;
     return (!GEN && !QRows<Tp>::LONG && Tp::QT == 1 && Tp::QCL <= 2 && (8 / W) * block <= 160L * 1024) ? 2 : 1;
