@@ -88,7 +88,16 @@ enum { JM_MOTOR_EFFORT_LIMIT = 1, JM_MOTOR_VELOCITY_LIMIT = 2, JM_MOTOR_FRICTION
  * frictionDryNegative, frictionDrySlope  (core/src/hardware/basic_motors.cc:83-143) */
 #define JM_MOTOR_NPARAMS 9
 
-/* ---- per-lane status bits written by the kernels */
+/* ---- per-lane status bits written by the kernels (JM_F_STATUS).  The contract ("Lane status contract"):
+ *  - the status of a lane belongs to that lane alone: a failed robot changes no number of another robot of the batch;
+ *  - `start`, `step` and the masked lanes of `reset_lanes` OVERWRITE the status: every bit then describes that launch and
+ *    nothing older.  NAN: the incoming q / v / a of a step or an acceleration of any evaluation of the launch; OUT_OF_BOUNDS
+ *    (spring-damper model only): any evaluation of the launch, `lower <= q <= upper` is inside; FORCE_OVERFLOW: `start` and
+ *    `reset_lanes` only, so the next step clears it; SOLVER_FAILURE: the LAST evaluation of the launch only;
+ *  - the refresh launch that closes an adaptive interval (extra terms, sensors) ORs its bits into the status;
+ *  - the adaptive stepper zeroes the status when `new_step` is set and carries it over otherwise; a lane that holds NAN or
+ *    STEPPER_FAILURE is frozen (neither state nor stepper state moves, `t` stays behind `t_next`) until the next call with
+ *    `new_step` or until `reset_lanes` -- the reference raises for its one robot there (engine.cc:2340-2384). */
 enum {
     JM_LANE_OK = 0,
     JM_LANE_NAN = 1,            /* NaN in q/v/a (engine.cc:1737-1747, abstract_stepper.cc:41-48) */

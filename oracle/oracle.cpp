@@ -2781,14 +2781,18 @@ void orc_batch_run_dopri(void * h, const orc_batch_io * io, const orc_adaptive_i
     ao.successiveIterFailedMax = succ_failed_max;
     for (int64_t l = lane_begin; l < lane_end; ++l)
     {
+        // the status contract of the adaptive entry points (jiminy_hip.h): zeroed on the first interval of an Engine::step,
+        // carried over on the later ones, where a lane that holds NAN or STEPPER_FAILURE is frozen: it is skipped outright,
+        // state, stepper state and outputs stay as the interval that flagged it left them
+        const int carried = (!new_step && io->status) ? io->status[l] : 0;
+        if (carried & (JM_LANE_NAN | JM_LANE_STEPPER_FAILURE)) continue;
         load_lane(e, *io, l);
-        e.status = io->status ? (io->status[l] & ~JM_LANE_OUT_OF_BOUNDS) : 0;
         AdaptiveState S;
         S.t = ad->t[l]; S.dt = ad->dt[l]; S.dtLargest = ad->dt_largest[l]; S.dtLargestPrev = ad->dt_largest_prev[l];
         S.iter = ad->iter[l]; S.iterFailed = ad->iter_failed[l];
         S.successiveIterTooLarge = new_step ? 0 : (int)ad->succ_too_large[l];
         S.successiveIterFailed = new_step ? 0 : (int)ad->succ_failed[l];
-        e.status = 0;
+        e.status = carried;
         step_dopri(e, S, ao, t_next, command_changed, update_sensors);
         ad->t[l] = S.t; ad->dt[l] = S.dt; ad->dt_largest[l] = S.dtLargest; ad->dt_largest_prev[l] = S.dtLargestPrev;
         ad->iter[l] = S.iter; ad->iter_failed[l] = S.iterFailed;

@@ -66,7 +66,7 @@ def _lib(model: CompiledModel) -> C.CDLL:
     return L
 
 
-MODES = {"step": 0, "start": 1, "dynamics": 2, "reset": 3}
+MODES = {"step": 0, "start": 1, "dynamics": 2, "reset": 3, "refresh": 4}      # (= jm::MODE_*)
 SOLVERS = {"euler_explicit": 0, "runge_kutta_4": 1}
 
 
@@ -134,6 +134,8 @@ def run_dopri(model: CompiledModel, arrays: Dict[str, np.ndarray], adaptive: Dic
     (robots still active, largest attempt count)."""
     L = _lib(model)
     B = arrays["q"].shape[-1]
+    if new_step:        # (as the library and the oracle do: the status of an Engine::step starts empty, jiminy_hip.h)
+        arrays["status"][:] = 0
     fs = np.zeros((len(_AD_F), B))
     isv = np.zeros((len(_AD_I), B), dtype=np.int32)
     for i, n in enumerate(_AD_F[:4]):
