@@ -682,6 +682,92 @@ int32_t jm_block_frame_average(const jm_frames_plan * plan, int32_t dtype, int64
                                const void * pose, double inv_step_dt, void * v_avg, void * pose_mean, void * quat_no_yaw,
                                void * stream);
 
+/* ---- Locomotion quantities: what a locomotion learner shapes rewards and terminations with, from what a step left in
+ * device memory; batched, one lane = one environment, one launch per refresh.  New symbols only: no existing structure or
+ * signature changed with them.  Reference: python/gym_jiminy/common/gym_jiminy/common/quantities/locomotion.py and
+ * compositions/locomotion.py, restated operation for operation.
+ * jm_locomotion_desc: the plan (host arrays, copied by jm_locomotion_plan_create).  `body_mass` of every joint (joint 0, the
+ *   universe, is not counted), the rotational inertia of the body of joint 1 in the order of JM_F_MODEL_LANE, `gravity` =
+ *   |gravity_z|, `omega` = the natural frequency of `CapturePoint.initialize` (quantities/locomotion.py:1097-1112:
+ *   sqrt(gravity / (com_z - lowest contact frame z)) at the neutral configuration), per contact point the foot it belongs to
+ *   (`contact_foot`, -1: none; the contacts of one foot must be consecutive, :1440-1449) and the column of its frame in the
+ *   tensors of the frame kinematics block (`contact_column`), the column of the root joint's frame (`root_column`), the
+ *   number of columns `n_frames` (the row stride of those tensors is `n_frames * B`), and the reference frame of the ZMP and
+ *   of the DCM (0 LOCAL = the odometry frame, 1 LOCAL_WORLD_ALIGNED).  jm_locomotion_plan_create validates the description
+ *   (JM_EINVAL + jm_last_error, before any device call: null arrays, sizes, masses, finite constants, positive gravity and
+ *   omega, reference frames, columns, foot indices, consecutive contacts, every foot with a contact) and uploads it; the
+ *   launch then allocates, copies and synchronises nothing.
+ * jm_locomotion_io: the device pointers of one launch, arrays `[rows][B]` of the scalar type `dtype`.  Every pointer may be
+ *   NULL: the outputs that need it are then not written.  Inputs: `centroidal` `[15][B]` (JM_F_CENTROIDAL); `q_root` the
+ *   first of the 7 root pose rows of `q`; `model_lane` (JM_F_MODEL_LANE `[13 * njoints][B]`: the mass of the robot is then
+ *   the sum of the lane's mass rows of joints 1 .. njoints - 1 and the root inertia the lane's); `con_lambda` the first
+ *   contact multiplier row of JM_F_CON_DATA (`[4 * n_contacts][B]`, behind the reference configurations and multipliers of
+ *   the bounds); `con_flags` the first contact row of JM_F_CON_FLAGS (int32 `[n_contacts][B]`; a contact whose bit 0 is clear
+ *   contributes zero, whatever its multiplier rows hold); `v_avg` `[6][K][B]`, `quat_no_yaw` `[4][K][B]`, `pose` `[7][K][B]`
+ *   of the frame kinematics block, K = n_frames (the root column of `v_avg` must be a LOCAL frame); `lane_mask` (uint8 `[B]`,
+ *   NULL: every lane; other lanes are not touched).  Outputs:
+ *     com[3], vcom[3]          `CenterOfMass` (:814-887); vcom = hg_linear / mass (core/src/engine/engine.cc:896)
+ *     odom_pose[3]             `BaseOdometryPose` (:158-219): x, y, atan2(sin_yaw, cos_yaw) of `quat_to_yaw_cos_sin`
+ *                              (utils/math.py:95-141)
+ *     zmp[2]                   `ZeroMomentPoint` (:914-1017): the NaN pair when |dhg_linear_z + weight| < float32 eps, in both
+ *                              scalar types; `translate_position_odom` (:891-910) for LOCAL
+ *     dcm[2]                   `CapturePoint` (:1021-1124)
+ *     h_angular[3]             `AverageBaseMomentum` (:344-412): root inertia times the angular half of the root's LOCAL
+ *                              `v_avg`, rotated by its `quat_no_yaw` (`quat_apply`, utils/math.py:645-709)
+ *     contact_force_rel[6][n_contacts]   `MultiContactNormalizedSpatialForce` (:1128-1268): rows 0-2 and 5 the multipliers over
+ *                              the weight, rows 3-4 zero
+ *     foot_force_vertical[n_feet]        `MultiFootNormalizedForceVertical` (:1272-1481) on flat ground (the vertical
+ *                              transform of every contact is e_z)
+ *     scalars[4]               0 force_vertical_max: the largest row 2 of contact_force_rel (`ImpactForceTermination`,
+ *                              compositions/locomotion.py:582-620); 1 ground_distance_min: `min_depth` on flat ground, the
+ *                              lowest contact frame z (`FlyingTermination`, :450-579); 2 reward_momentum =
+ *                              `radial_basis_function(h_angular, momentum_cutoff, 2)` (`MinimizeAngularMomentumReward`,
+ *                              :257-281; compositions/mixin.py:17-66, CUTOFF_ESP = 1e-2); 3 reward_friction = the same of
+ *                              rows 0-1 of contact_force_rel with `friction_cutoff` (`MinimizeFrictionReward`, :284-315).
+ *                              A non-positive cutoff: that row is not written. */
+typedef struct jm_locomotion_desc
+{
+    int32_t njoints;
+    const double * body_mass;           /* [njoints] */
+    const double * root_inertia;        /* [6] xx xy xz yy yz zz */
+    double gravity;
+    double omega;
+    int32_t n_contacts;
+    int32_t n_feet;
+    const int32_t * contact_foot;       /* [n_contacts], -1: no foot */
+    const int32_t * contact_column;     /* [n_contacts] */
+    int32_t n_frames;
+    int32_t root_column;
+    int32_t zmp_frame;
+    int32_t dcm_frame;
+} jm_locomotion_desc;
+typedef struct jm_locomotion_io
+{
+    const void * centroidal;
+    const void * q_root;
+    const void * model_lane;
+    const void * con_lambda;
+    const int32_t * con_flags;
+    const void * v_avg;
+    const void * quat_no_yaw;
+    const void * pose;
+    const uint8_t * lane_mask;
+    void * com;
+    void * vcom;
+    void * odom_pose;
+    void * zmp;
+    void * dcm;
+    void * h_angular;
+    void * contact_force_rel;
+    void * foot_force_vertical;
+    void * scalars;
+} jm_locomotion_io;
+typedef struct jm_locomotion_plan jm_locomotion_plan;
+int32_t jm_locomotion_plan_create(const jm_locomotion_desc * desc, jm_locomotion_plan ** out);
+int32_t jm_locomotion_plan_destroy(jm_locomotion_plan * plan);
+int32_t jm_block_locomotion(const jm_locomotion_plan * plan, int32_t dtype, int64_t batch_size, const jm_locomotion_io * io,
+                            double momentum_cutoff, double friction_cutoff, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

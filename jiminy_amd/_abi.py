@@ -109,6 +109,25 @@ class FramesDesc(C.Structure):
     ]
 
 
+class LocomotionDesc(C.Structure):
+    """jm_locomotion_desc: the plan of the locomotion quantities (jiminy_amd.locomotion builds it)."""
+    _fields_ = [
+        ("njoints", C.c_int32), ("body_mass", _pd), ("root_inertia", _pd), ("gravity", C.c_double), ("omega", C.c_double),
+        ("n_contacts", C.c_int32), ("n_feet", C.c_int32), ("contact_foot", _pi), ("contact_column", _pi),
+        ("n_frames", C.c_int32), ("root_column", C.c_int32), ("zmp_frame", C.c_int32), ("dcm_frame", C.c_int32),
+    ]
+
+
+LOCOMOTION_IO_FIELDS = ("centroidal", "q_root", "model_lane", "con_lambda", "con_flags", "v_avg", "quat_no_yaw", "pose",
+                        "lane_mask", "com", "vcom", "odom_pose", "zmp", "dcm", "h_angular", "contact_force_rel",
+                        "foot_force_vertical", "scalars")
+
+
+class LocomotionIO(C.Structure):
+    """jm_locomotion_io: the device pointers of one launch of jm_block_locomotion, each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in LOCOMOTION_IO_FIELDS]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

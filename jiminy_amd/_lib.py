@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "jm_attitude_plan_create", "jm_attitude_plan_destroy", "jm_block_attitude_init", "jm_block_mahony_observer",
     "jm_block_body_observer",
     "jm_frames_plan_create", "jm_frames_plan_destroy", "jm_block_frame_kinematics", "jm_block_frame_average",
+    "jm_locomotion_plan_create", "jm_locomotion_plan_destroy", "jm_block_locomotion",
 )
 
 
@@ -119,6 +120,9 @@ class HipLibrary:
         L.jm_frames_plan_destroy.argtypes = [vp]
         L.jm_block_frame_kinematics.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.jm_block_frame_average.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp]
+        L.jm_locomotion_plan_create.argtypes = [C.POINTER(_abi.LocomotionDesc), C.POINTER(vp)]
+        L.jm_locomotion_plan_destroy.argtypes = [vp]
+        L.jm_block_locomotion.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.LocomotionIO), C.c_double, C.c_double, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

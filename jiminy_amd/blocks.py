@@ -27,6 +27,11 @@ refresh (csrc/jm_attitude.h) driven by a plan that jiminy_amd/attitude.py builds
 `FrameKinematics` gives the pose and the velocity of named frames and their SE3 average over an environment step (what the
 reference's quantity layer reads from `pinocchio_data.oMf` and `getFrameVelocity`): one HIP launch each (csrc/jm_frames.h) driven
 by a plan that jiminy_amd/frames.py builds; specification of the average: tests/golden/ref_frames.npz.
+
+`LocomotionQuantities` gives the balance quantities of a legged robot (centre of mass, odometry pose, ZMP, capture point, base
+momentum, normalised contact and foot forces, the scalars of two rewards and two terminations) from what a step left on the
+device and from the tensors of a `FrameKinematics`: one HIP launch per refresh (csrc/jm_locomotion.h) driven by a plan that
+jiminy_amd/locomotion.py builds; specification: tests/golden/ref_locomotion.npz.
 """
 from __future__ import annotations
 
@@ -479,6 +484,172 @@ class FrameKinematics:
         if plan:
             try:
                 self._L.jm_frames_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+LOCOMOTION_SCALARS = ("force_vertical_max", "ground_distance_min", "reward_momentum", "reward_friction")
+
+
+def locomotion_fieldnames(contact_names, foot_frame_names, momentum: bool, forces: bool):
+    """Names of the rows of the tensors of a `LocomotionQuantities` block."""
+    xyz = ("X", "Y", "Z")
+    names = {"com": [f"Com.{e}" for e in xyz], "vcom": [f"ComVelocity.{e}" for e in xyz],
+             "odom_pose": ["Odom.X", "Odom.Y", "Odom.Yaw"], "zmp": ["Zmp.X", "Zmp.Y"], "dcm": ["Dcm.X", "Dcm.Y"],
+             "scalars": list(LOCOMOTION_SCALARS)}
+    if momentum:
+        names["h_angular"] = [f"BaseMomentum.Ang{e}" for e in xyz]
+    if forces:
+        names["contact_force_rel"] = [[f"{n}.{e}" for n in contact_names] for e in ("LinX", "LinY", "LinZ", "AngX", "AngY", "AngZ")]
+        names["foot_force_vertical"] = [f"{n}.ForceVertical" for n in foot_frame_names]
+    return names
+
+
+class LocomotionQuantities:
+    """The balance quantities of the reference's locomotion layer (quantities/locomotion.py, compositions/locomotion.py) per
+    lane, from what a step left on the device: `com`, `vcom` `[3][B]` ≙ `CenterOfMass` (:814-887); `odom_pose` `[3][B]` ≙
+    `BaseOdometryPose` (:158-219); `zmp` `[2][B]` ≙ `ZeroMomentPoint` (:914-1017; NaN in free fall); `dcm` `[2][B]` ≙
+    `CapturePoint` (:1021-1124); `h_angular` `[3][B]` ≙ `AverageBaseMomentum` (:344-412; `momentum`, else None);
+    `contact_force_rel` `[6][n_contacts][B]` ≙ `MultiContactNormalizedSpatialForce` (:1128-1268) and `foot_force_vertical`
+    `[n_feet][B]` ≙ `MultiFootNormalizedForceVertical` (:1272-1481) on flat ground (`forces`, else None); `scalars` `[4][B]`,
+    rows `LOCOMOTION_SCALARS`: the largest normalised vertical contact force (`ImpactForceTermination`), the height of the lowest
+    contact frame (`FlyingTermination`), and `MinimizeAngularMomentumReward` / `MinimizeFrictionReward` with `momentum_cutoff` /
+    `friction_cutoff` (None: that row stays zero).
+
+    `frames`: the `FrameKinematics` block of the same engine, holding 'root_joint' (LOCAL) and every contact frame, with
+    `average=True` unless `momentum=False`; refresh it first.  The force quantities need the constraint contact model
+    (`forces=False` leaves them out).  `refresh()` is one launch on the engine's stream, without allocation, copy or
+    synchronisation; `reset(lane_mask)` evaluates the masked lanes (every lane without a mask) at the state the engine's
+    `start` / `reset_lanes` wrote and keeps the others bit for bit.  The tensors never change identity."""
+
+    def __init__(self, engine, frames: "FrameKinematics", *, foot_frame_names="auto", zmp_reference_frame="LOCAL",
+                 dcm_reference_frame="LOCAL", momentum_cutoff: Optional[float] = None, friction_cutoff: Optional[float] = None,
+                 momentum: bool = True, forces: bool = True) -> None:
+        import ctypes as C
+
+        from . import _abi, locomotion
+        from . import frames as frames_
+        model = engine.model
+        if not model.has_freeflyer:
+            raise ValueError("Only legged robot with floating base are supported: the model has no free-flyer.")
+        if "centroidal" not in engine._fields:
+            raise ValueError("the locomotion quantities read the 'centroidal' output of the engine: build it with "
+                             "extra_outputs=(..., 'centroidal') or call enable_output('centroidal')")
+        if frames._eng is not engine:
+            raise ValueError("the frame kinematics block belongs to another engine")
+        for cutoff in (momentum_cutoff, friction_cutoff):
+            if cutoff is not None and not float(cutoff) > 0.0:
+                raise ValueError("a reward cutoff must be positive")
+        constraint_model = engine._options["contacts"]["model"] == "constraint"
+        self.momentum, self.forces = bool(momentum), bool(forces)
+        if (momentum_cutoff is not None and not self.momentum) or (friction_cutoff is not None and not self.forces):
+            raise ValueError("a reward cutoff was given for a quantity that is switched off")
+        if self.momentum and not frames.average:
+            raise ValueError("the angular momentum reads the step average of the root frame: build the frame kinematics "
+                             "block with average=True (or pass momentum=False)")
+        if self.forces and not constraint_model:
+            raise NotImplementedError("the contact force quantities read the multipliers of the contact constraints "
+                                      "(`lambda_c`): contacts.model = 'spring_damper' has none (pass forces=False for the "
+                                      "other quantities)")
+        if engine._ground is not None:
+            raise NotImplementedError("the locomotion quantities assume flat ground: on a height map the local contact frame "
+                                      "is the surface's")
+        self.plan = locomotion.build_plan(model, frames.frame_names, foot_frame_names=foot_frame_names,
+                                          zmp_reference_frame=zmp_reference_frame, dcm_reference_frame=dcm_reference_frame)
+        if self.momentum and frames.plan.modes[frames.index("root_joint")] != frames_.LOCAL:
+            raise ValueError("the angular momentum reads the LOCAL step-average velocity of 'root_joint': the frame kinematics "
+                             "block holds it in another reference frame")
+        self._C = C
+        self._eng, self._frames = engine, frames
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.foot_frame_names = list(self.plan.foot_frame_names)
+        self.momentum_cutoff = None if momentum_cutoff is None else float(momentum_cutoff)
+        self.friction_cutoff = None if friction_cutoff is None else float(friction_cutoff)
+        B, nc = engine.batch_size, self.plan.n_contacts
+        new = lambda *shape: torch.zeros((*shape, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
+        self.com, self.vcom, self.odom_pose, self.zmp, self.dcm, self.scalars = new(3), new(3), new(3), new(2), new(2), new(4)
+        self.h_angular = new(3) if self.momentum else None
+        self.contact_force_rel = new(6, nc) if self.forces else None
+        self.foot_force_vertical = new(self.plan.n_feet) if self.forces else None
+        rows = _abi.constraint_rows(model)
+        self._flag_row, self._lambda_row = rows["n_bounds"], 2 * rows["n_bounds"]
+        self._q_row = int(model.idx_q[1])
+        self._io = _abi.LocomotionIO()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_locomotion_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        return locomotion_fieldnames(self._eng.model.contacts, self.foot_frame_names, self.momentum, self.forces)
+
+    @property
+    def force_vertical_max(self) -> torch.Tensor:
+        return self.scalars[0]
+
+    @property
+    def ground_distance_min(self) -> torch.Tensor:
+        return self.scalars[1]
+
+    @property
+    def reward_momentum(self) -> torch.Tensor:
+        return self.scalars[2]
+
+    @property
+    def reward_friction(self) -> torch.Tensor:
+        return self.scalars[3]
+
+    def _launch(self, mask: Optional[torch.Tensor]) -> None:
+        eng, fr, io = self._eng, self._frames, self._io
+
+        def ptr(t: Optional[torch.Tensor], dtype=None):
+            if t is None:
+                return None
+            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
+                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+            return t.data_ptr()
+        io.centroidal, io.q_root = ptr(eng.field("centroidal")), ptr(eng.field("q")[self._q_row:self._q_row + 7])
+        io.model_lane = ptr(eng._fields.get("model_lane"))
+        io.con_lambda = io.con_flags = None
+        if self.forces:
+            # (the constraint state of the engine exists once the constraint contact model is selected)
+            flags, data = eng._fields["con_flags"], eng._fields["con_data"]
+            nc = self.plan.n_contacts
+            io.con_flags = ptr(flags[self._flag_row:self._flag_row + nc], torch.int32)
+            io.con_lambda = ptr(data[self._lambda_row:self._lambda_row + 4 * nc])
+        io.v_avg = ptr(fr.average_velocity) if self.momentum else None
+        io.quat_no_yaw = ptr(fr.quat_no_yaw) if self.momentum else None
+        io.pose = ptr(fr.pose)
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        for name in ("com", "vcom", "odom_pose", "zmp", "dcm", "h_angular", "contact_force_rel", "foot_force_vertical", "scalars"):
+            setattr(io, name, ptr(getattr(self, name)))
+        self._check(self._L.jm_block_locomotion(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
+                                                self.momentum_cutoff or 0.0, self.friction_cutoff or 0.0, eng._stream()))
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The quantities at the state of a new episode on the masked lanes (every lane without a mask); the other lanes
+        keep every tensor bit for bit.  Call it after the engine's `start` / `reset_lanes` and the reset of `frames`."""
+        eng = self._eng
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        self._launch(mask)
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream, behind the refresh (and the step average) of `frames`."""
+        self._launch(None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_locomotion_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families and of the frame kinematics, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics and of the locomotion quantities, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "jm_deform.h"
 #include "jm_attitude.h"
 #include "jm_frames.h"
+#include "jm_locomotion.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -88,6 +89,11 @@ struct jm_attitude_plan
 };
 // frame kinematics and its step average (jm_frames.h)
 struct jm_frames_plan
+{
+    DevicePlan dev;
+};
+// the locomotion quantities (jm_locomotion.h)
+struct jm_locomotion_plan
 {
     DevicePlan dev;
 };
@@ -312,6 +318,35 @@ int32_t jm_block_frame_average(const jm_frames_plan * p, int32_t dtype, int64_t 
         using T = decltype(z);
         hipLaunchKernelGGL((jm::k_frame_average<T>), grid, dim3(256), 0, s, a, (T *)pose_prev, (const T *)pose, inv_step_dt,
                            (T *)v_avg, (T *)pose_mean, (T *)quat_no_yaw, (long long)B);
+    });
+}
+
+int32_t jm_locomotion_plan_create(const jm_locomotion_desc * desc, jm_locomotion_plan ** out)
+{
+    return plan_create("jm_locomotion_plan_create", desc, out, jm::locomotion_pack);
+}
+
+int32_t jm_locomotion_plan_destroy(jm_locomotion_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_locomotion(const jm_locomotion_plan * p, int32_t dtype, int64_t B, const jm_locomotion_io * io,
+                            double momentum_cutoff, double friction_cutoff, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_locomotion: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_locomotion: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_locomotion: bad dtype");
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::LocoIO<T> a{(const T *)io->centroidal, (const T *)io->q_root, (const T *)io->model_lane, (const T *)io->con_lambda,
+                              io->con_flags, (const T *)io->v_avg, (const T *)io->quat_no_yaw, (const T *)io->pose, io->lane_mask,
+                              (T *)io->com, (T *)io->vcom, (T *)io->odom_pose, (T *)io->zmp, (T *)io->dcm, (T *)io->h_angular,
+                              (T *)io->contact_force_rel, (T *)io->foot_force_vertical, (T *)io->scalars};
+        hipLaunchKernelGGL((jm::k_locomotion<T>), grid, dim3(256), 0, s, it, dt, a, momentum_cutoff, friction_cutoff, (long long)B);
     });
 }
 

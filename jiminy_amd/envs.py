@@ -429,7 +429,7 @@ class WalkerVecEnv(VecJiminyEnv):
 
     def __init__(self, *args: Any, reward_mixture: Optional[Dict[str, float]] = None,
                  frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
-                 **kw: Any) -> None:
+                 locomotion_quantities: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -439,16 +439,37 @@ class WalkerVecEnv(VecJiminyEnv):
         #   min_base_height=(value, grace_period)      ≙ `FallingTermination` (:358-398) on `base_relative_height()`
         # a lane terminates when its episode time has reached the grace period and the value has left [low, high]
         # (bases/compositions.py:560-571, 647-663).  With both None nothing of this exists.
-        self.frames = None
+        # optional `blocks.LocomotionQuantities` (its constructor's keywords), refreshed behind the frames block, reset with
+        # it and exposed as `locomotion`; the terminations and reward terms that read it:
+        #   flying=(max_height, grace_period)          ≙ `FlyingTermination` (compositions/locomotion.py:543-579)
+        #   impact_force=(max_force_rel, grace_period) ≙ `ImpactForceTermination` (:582-620)
+        #   reward_mixture['momentum'] / ['friction']  ≙ `MinimizeAngularMomentumReward` / `MinimizeFrictionReward` (:257-315),
+        #                                              weights on the reward rows of the block's `momentum_cutoff` / `friction_cutoff`
+        self.frames = self.locomotion = None
         self._terminations = dict(terminations or {})
-        unknown = set(self._terminations) - {"base_roll_pitch", "min_base_height"}
+        known = ("base_roll_pitch", "min_base_height", "flying", "impact_force")
+        unknown = set(self._terminations) - set(known)
         if unknown:
-            raise ValueError(f"unknown terminations {sorted(unknown)} (base_roll_pitch, min_base_height)")
+            raise ValueError(f"unknown terminations {sorted(unknown)} ({', '.join(known)})")
+        if {"flying", "impact_force"} & set(self._terminations) and locomotion_quantities is None:
+            raise ValueError("the flying and impact_force terminations read the locomotion quantities block: give "
+                             "locomotion_quantities as well")
+        if locomotion_quantities is not None:
+            frame_kinematics = {} if frame_kinematics is None else frame_kinematics
+            for term, cutoff in (("momentum", "momentum_cutoff"), ("friction", "friction_cutoff")):
+                if term in self.reward_mixture and locomotion_quantities.get(cutoff) is None:
+                    raise ValueError(f"reward_mixture['{term}'] needs locomotion_quantities['{cutoff}']")
+        elif {"momentum", "friction"} & set(self.reward_mixture):
+            raise ValueError("the momentum and friction reward terms read the locomotion quantities block: give "
+                             "locomotion_quantities as well")
         if self._terminations and frame_kinematics is None:
             raise ValueError("the terminations read the frame kinematics block: give frame_kinematics as well")
         if frame_kinematics is not None:
-            names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, self._terminations)
+            names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, self._terminations, locomotion_quantities)
             self.frames = blocks.FrameKinematics(self.engine, names, reference_frames=modes, **cfg)
+            if locomotion_quantities is not None:
+                self.engine.enable_output("centroidal")
+                self.locomotion = blocks.LocomotionQuantities(self.engine, self.frames, **locomotion_quantities)
             if self._terminations:
                 self._frame_root = self.frames.index("root_joint")
                 self._frame_contacts = torch.tensor([self.frames.index(n) for n in self.model.contacts], dtype=torch.long, device=self.device)
@@ -474,18 +495,19 @@ class WalkerVecEnv(VecJiminyEnv):
         self._dir_n = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
 
     @staticmethod
-    def frame_kinematics_config(model: CompiledModel, frame_kinematics: Dict[str, Any], terminations: Dict[str, Any]
+    def frame_kinematics_config(model: CompiledModel, frame_kinematics: Dict[str, Any], terminations: Dict[str, Any],
+                                locomotion_quantities: Optional[Dict[str, Any]] = None
                                 ) -> Tuple[list, Optional[list], Dict[str, Any]]:
         """Frame names, reference frames and remaining keywords of the `blocks.FrameKinematics` of an environment: the
-        user's, plus what the terminations read where it is missing -- the root joint and every contact frame (LOCAL), and
-        the Euler angles for `base_roll_pitch`."""
+        user's, plus what the terminations and the locomotion quantities read where it is missing -- the root joint and
+        every contact frame (LOCAL), the Euler angles for `base_roll_pitch` and the step average for the angular momentum."""
         cfg = dict(frame_kinematics)
         names = list(cfg.pop("frame_names", ()))
         modes = cfg.pop("reference_frames", None)
         modes = None if modes is None else list(modes)
         if modes is not None and len(modes) != len(names):
             raise ValueError(f"expected one reference frame per frame ({len(names)}), got {len(modes)}")
-        if terminations:
+        if terminations or locomotion_quantities is not None:
             for name in ["root_joint"] + list(model.contacts):
                 if name not in names:
                     names.append(name)
@@ -493,6 +515,8 @@ class WalkerVecEnv(VecJiminyEnv):
                         modes.append("LOCAL")
             if "base_roll_pitch" in terminations:
                 cfg["compute_rpy"] = True
+            if locomotion_quantities is not None and locomotion_quantities.get("momentum", True):
+                cfg["average"] = True
         return names, modes, cfg
 
     def _direction_restart(self, lane_mask: Optional[torch.Tensor]) -> None:
@@ -509,6 +533,8 @@ class WalkerVecEnv(VecJiminyEnv):
         self._direction_restart(None)
         if self.frames is not None:
             self.frames.reset(None)
+        if self.locomotion is not None:
+            self.locomotion.reset(None)
         return out
 
     def reset_lanes(self, lane_mask: torch.Tensor) -> None:
@@ -516,6 +542,8 @@ class WalkerVecEnv(VecJiminyEnv):
         self._direction_restart(lane_mask)
         if self.frames is not None:
             self.frames.reset(lane_mask)
+        if self.locomotion is not None:
+            self.locomotion.reset(lane_mask)
 
     def _after_step(self):
         self._dir_sum += self.engine.robot_state.q[1].to(torch.float64)
@@ -524,6 +552,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.refresh()
             if self.frames.average:
                 self.frames.refresh_average(self.step_dt)
+        if self.locomotion is not None:
+            self.locomotion.refresh()
         return super()._after_step()
 
     def base_relative_height(self) -> torch.Tensor:
@@ -547,6 +577,12 @@ class WalkerVecEnv(VecJiminyEnv):
             if "min_base_height" in self._terminations:
                 value, grace = self._terminations["min_base_height"]
                 terminated = terminated | ((t >= grace) & (self.base_relative_height() < value))
+            if "flying" in self._terminations:
+                max_height, grace = self._terminations["flying"]
+                terminated = terminated | ((t >= grace) & (self.locomotion.ground_distance_min > max_height))
+            if "impact_force" in self._terminations:
+                max_force_rel, grace = self._terminations["impact_force"]
+                terminated = terminated | ((t >= grace) & (self.locomotion.force_vertical_max > max_force_rel))
         return terminated, truncated
 
     def compute_reward(self, terminated: torch.Tensor) -> torch.Tensor:
@@ -565,6 +601,10 @@ class WalkerVecEnv(VecJiminyEnv):
             # at termination only: minus the absolute mean lateral position of the episode (locomotion.py:419-424)
             drift = (self._dir_sum / torch.clamp_min(self._dir_n, 1.0)).abs().to(self.dtype)
             total -= self.reward_mixture["direction"] * drift * terminated.to(self.dtype)
+        if "momentum" in self.reward_mixture:
+            total += self.reward_mixture["momentum"] * self.locomotion.reward_momentum
+        if "friction" in self.reward_mixture:
+            total += self.reward_mixture["friction"] * self.locomotion.reward_friction
         return total
 
 
