@@ -768,6 +768,81 @@ int32_t jm_locomotion_plan_destroy(jm_locomotion_plan * plan);
 int32_t jm_block_locomotion(const jm_locomotion_plan * plan, int32_t dtype, int64_t batch_size, const jm_locomotion_io * io,
                             double momentum_cutoff, double friction_cutoff, void * stream);
 
+/* ---- Actuated-joint quantities: kinematics of the actuated joints in motor order, distances to the mechanical stops, the
+ * mechanical-safety count, the mechanical power, its sliding average over environment steps and the reward on it; batched,
+ * one lane = one environment, one launch per refresh.  New symbols only: no existing structure or signature changed with
+ * them.  Reference: python/gym_jiminy/common/gym_jiminy/common/quantities/generic.py:1538-1887 and
+ * compositions/generic.py:153-191, 456-661, restated operation for operation.
+ * jm_actuation_desc: the plan (host arrays, copied by jm_actuation_plan_create).  Per motor, in motor order: the row of its
+ *   joint in `q` (`idx_q`) and in `v` / `a` (`idx_v`), its mechanical reduction (`MultiActuatedJointKinematic.initialize`,
+ *   quantities/generic.py:1626-1645) and the position bounds of that row (`_MultiActuatedJointBoundDistance.initialize`,
+ *   compositions/generic.py:486-498); `nq` / `nv` the rows of `q` / `v`; `generator_mode` the `EnergyGenerationMode`
+ *   (quantities/generic.py:1694-1719: 0 CHARGE, 1 LOST_EACH, 2 LOST_GLOBAL, 3 PENALIZE); `max_stack` the length of the sliding
+ *   window (`AverageMechanicalPowerConsumption.__init__`, :1865: max(ceil(horizon / step_dt), 1) + 1).
+ *   jm_actuation_plan_create validates the description (JM_EINVAL + jm_last_error, before any device call: null arrays,
+ *   1 <= n_motors <= 256, indices inside nq / nv, finite reductions and bounds, low <= high, the generator mode,
+ *   2 <= max_stack <= 1024) and uploads it; the launch then allocates, copies and synchronises nothing.
+ * jm_actuation_io: the device pointers of one launch, arrays `[rows][B]` of the scalar type `dtype` but the three integer
+ *   ones.  Every pointer may be NULL: the outputs that need it are then not written.  Inputs: `q` `[nq][B]`, `v`, `a`
+ *   `[nv][B]`, `command` `[n_motors][B]` (the motor efforts), `lane_mask` (uint8 `[B]`, NULL: every lane; other lanes are
+ *   not touched).  State, owned by the caller: `power_ring` `[max_stack][B]`, `power_count` (int32 `[B]`, the `num_steps` of
+ *   the reference's stack per lane).  Outputs, each in motor order:
+ *     position, velocity, acceleration [n_motors]   `MultiActuatedJointKinematic.refresh` (quantities/generic.py:1675-1691):
+ *                              the row of the state, times the reduction when `motor_side` is non-zero (one flag for the
+ *                              three levels)
+ *     bound_low, bound_high [n_motors]   `_MultiActuatedJointBoundDistance.refresh` (compositions/generic.py:500-502):
+ *                              position - low, high - position on the joint side, whatever `motor_side`
+ *     safety (int32 [B])       the number of motors with (bound_low < position_margin) & (v < -velocity_max) or
+ *                              (bound_high < position_margin) & (v > velocity_max), v on the joint side
+ *                              (`MechanicalSafetyTermination.compute`, :585-595: it terminates when the count is not
+ *                              zero).  A negative `velocity_max`: not written.
+ *     scalars[3]               0 power: `compute_power` (quantities/generic.py:1723-1746) of `command` and v * reduction;
+ *                              1 power_average: `AverageMechanicalPowerConsumption.refresh` (:1886-1887), `np.sum / size` over
+ *                              the wrapping stack of `StackedQuantity.refresh` (quantities/transform.py:208-296); 2
+ *                              reward_power = `radial_basis_function(power_average, power_cutoff, 2)`
+ *                              (`MinimizeMechanicalPowerConsumption`, compositions/generic.py:153-191).  A non-positive
+ *                              cutoff: row 2 is not written; without the ring or the counter: rows 1-2 are not written.
+ * jm_block_actuation: `mode` 0 restarts the window of the launched lanes (count = 0, slot 0 = the current power, the average
+ *   is that value: what the first refresh of an episode gives), `mode` 1 pushes (count += 1, slot count % max_stack = the
+ *   current power, the average over the first min(count + 1, max_stack) slots in storage order).  No argument changes from
+ *   step to step, so the launch can be part of a captured graph. */
+typedef struct jm_actuation_desc
+{
+    int32_t n_motors;
+    int32_t nq;
+    int32_t nv;
+    const int32_t * idx_q;              /* [n_motors] */
+    const int32_t * idx_v;              /* [n_motors] */
+    const double * reduction;           /* [n_motors] */
+    const double * position_low;        /* [n_motors] */
+    const double * position_high;       /* [n_motors] */
+    int32_t generator_mode;
+    int32_t max_stack;
+} jm_actuation_desc;
+typedef struct jm_actuation_io
+{
+    const void * q;
+    const void * v;
+    const void * a;
+    const void * command;
+    const uint8_t * lane_mask;
+    void * position;
+    void * velocity;
+    void * acceleration;
+    void * bound_low;
+    void * bound_high;
+    int32_t * safety;
+    void * scalars;
+    void * power_ring;
+    int32_t * power_count;
+} jm_actuation_io;
+typedef struct jm_actuation_plan jm_actuation_plan;
+int32_t jm_actuation_plan_create(const jm_actuation_desc * desc, jm_actuation_plan ** out);
+int32_t jm_actuation_plan_destroy(jm_actuation_plan * plan);
+int32_t jm_block_actuation(const jm_actuation_plan * plan, int32_t dtype, int64_t batch_size, const jm_actuation_io * io,
+                           int32_t mode, int32_t motor_side, double position_margin, double velocity_max, double power_cutoff,
+                           void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

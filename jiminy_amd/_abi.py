@@ -128,6 +128,23 @@ class LocomotionIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in LOCOMOTION_IO_FIELDS]
 
 
+class ActuationDesc(C.Structure):
+    """jm_actuation_desc: the plan of the actuated-joint quantities (jiminy_amd.actuation builds it)."""
+    _fields_ = [
+        ("n_motors", C.c_int32), ("nq", C.c_int32), ("nv", C.c_int32), ("idx_q", _pi), ("idx_v", _pi), ("reduction", _pd),
+        ("position_low", _pd), ("position_high", _pd), ("generator_mode", C.c_int32), ("max_stack", C.c_int32),
+    ]
+
+
+ACTUATION_IO_FIELDS = ("q", "v", "a", "command", "lane_mask", "position", "velocity", "acceleration", "bound_low", "bound_high",
+                       "safety", "scalars", "power_ring", "power_count")
+
+
+class ActuationIO(C.Structure):
+    """jm_actuation_io: the device pointers of one launch of jm_block_actuation, each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in ACTUATION_IO_FIELDS]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "jm_block_body_observer",
     "jm_frames_plan_create", "jm_frames_plan_destroy", "jm_block_frame_kinematics", "jm_block_frame_average",
     "jm_locomotion_plan_create", "jm_locomotion_plan_destroy", "jm_block_locomotion",
+    "jm_actuation_plan_create", "jm_actuation_plan_destroy", "jm_block_actuation",
 )
 
 
@@ -123,6 +124,10 @@ class HipLibrary:
         L.jm_locomotion_plan_create.argtypes = [C.POINTER(_abi.LocomotionDesc), C.POINTER(vp)]
         L.jm_locomotion_plan_destroy.argtypes = [vp]
         L.jm_block_locomotion.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.LocomotionIO), C.c_double, C.c_double, vp]
+        L.jm_actuation_plan_create.argtypes = [C.POINTER(_abi.ActuationDesc), C.POINTER(vp)]
+        L.jm_actuation_plan_destroy.argtypes = [vp]
+        L.jm_block_actuation.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.ActuationIO), C.c_int32, C.c_int32, C.c_double,
+                                         C.c_double, C.c_double, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

@@ -32,6 +32,11 @@ by a plan that jiminy_amd/frames.py builds; specification of the average: tests/
 momentum, normalised contact and foot forces, the scalars of two rewards and two terminations) from what a step left on the
 device and from the tensors of a `FrameKinematics`: one HIP launch per refresh (csrc/jm_locomotion.h) driven by a plan that
 jiminy_amd/locomotion.py builds; specification: tests/golden/ref_locomotion.npz.
+
+`ActuatedJointQuantities` gives the actuated-joint part of the quantity layer (joint kinematics in motor order, distances to
+the mechanical stops, the mechanical-safety count, the mechanical power, its sliding average over environment steps and the
+reward on it) from the engine's `q / v / a / command`: one HIP launch per refresh (csrc/jm_actuation.h) driven by a plan that
+jiminy_amd/actuation.py builds; specification: tests/golden/ref_actuation.npz.
 """
 from __future__ import annotations
 
@@ -650,6 +655,141 @@ class LocomotionQuantities:
         if plan:
             try:
                 self._L.jm_locomotion_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+ACTUATION_SCALARS = ("power", "power_average", "reward_power")
+
+
+def actuation_fieldnames(motor_names):
+    """Names of the rows of the tensors of an `ActuatedJointQuantities` block."""
+    names = {k: [f"{n}.{label}" for n in motor_names]
+             for k, label in (("position", "Position"), ("velocity", "Velocity"), ("acceleration", "Acceleration"),
+                              ("bound_low", "BoundLow"), ("bound_high", "BoundHigh"))}
+    names["scalars"] = list(ACTUATION_SCALARS)
+    return names
+
+
+class ActuatedJointQuantities:
+    """The actuated-joint part of the reference's quantity layer (quantities/generic.py:1538-1887, compositions/generic.py:
+    153-191, 456-661) per lane, from the engine's `q / v / a / command`, each tensor in motor order: `position`, `velocity`,
+    `acceleration` `[M][B]` ≙ `MultiActuatedJointKinematic` (:1538-1691; `motor_side`: all three times the mechanical reduction);
+    `bound_low`, `bound_high` `[M][B]` ≙ `_MultiActuatedJointBoundDistance` (compositions/generic.py:456-502; always joint side);
+    `safety` `[B]` int32: the number of motors inside `position_margin` of a stop and approaching it faster than `velocity_max`
+    (`MechanicalSafetyTermination`, :505-595; both None: not evaluated); `scalars` `[3][B]`, rows `ACTUATION_SCALARS`: the
+    mechanical power ≙ `MechanicalPowerConsumption` in `generator_mode` (quantities/generic.py:1694-1812), its average over the
+    last `power_horizon` seconds of environment steps ≙ `AverageMechanicalPowerConsumption` (:1819-1887; None: no window, the
+    row stays zero and `power_average` raises), and `MinimizeMechanicalPowerConsumption` with `power_cutoff` on that average
+    (compositions/generic.py:153-191; None: the row stays zero).
+
+    The window is state of the block: `power_ring` `[max_stack][B]` and `power_count` `[B]`, the number of pushes of every lane
+    since its restart.  `reset(lane_mask)` restarts the windows of the masked lanes (every lane without a mask) at the state
+    the engine's `start` / `reset_lanes` wrote and keeps the other lanes bit for bit; `refresh()` pushes one environment step:
+    call it once per step.  Both are one launch on the engine's stream, without allocation, copy or synchronisation, and no
+    launch argument changes from step to step.  The tensors never change identity.  One window per block: a reward and a
+    termination on different horizons take two blocks."""
+
+    def __init__(self, engine, *, generator_mode="CHARGE", power_horizon: Optional[float] = None,
+                 power_cutoff: Optional[float] = None, position_margin: Optional[float] = None,
+                 velocity_max: Optional[float] = None, motor_side: bool = False, step_dt: Optional[float] = None) -> None:
+        import ctypes as C
+
+        from . import _abi, actuation
+        if power_cutoff is not None and not float(power_cutoff) > 0.0:
+            raise ValueError("a reward cutoff must be positive")
+        if power_cutoff is not None and power_horizon is None:
+            raise ValueError("power_cutoff rewards the average power: give power_horizon as well")
+        if (position_margin is None) != (velocity_max is None):
+            raise ValueError("the mechanical-safety count needs position_margin and velocity_max together")
+        if velocity_max is not None and (not float(velocity_max) >= 0.0 or not float(position_margin) >= 0.0):
+            raise ValueError("position_margin and velocity_max must not be negative")
+        self.plan = actuation.build_plan(engine.model, generator_mode=generator_mode, power_horizon=power_horizon, step_dt=step_dt)
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.motor_side = bool(motor_side)
+        self.power_cutoff = None if power_cutoff is None else float(power_cutoff)
+        self.position_margin = None if position_margin is None else float(position_margin)
+        self.velocity_max = None if velocity_max is None else float(velocity_max)
+        B, M = engine.batch_size, self.plan.n_motors
+        new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
+        self.position, self.velocity, self.acceleration, self.bound_low, self.bound_high = (new(M) for _ in range(5))
+        self.scalars, self.safety = new(3), new(dtype=torch.int32)
+        self.power_ring, self.power_count = new(self.plan.max_stack), new(dtype=torch.int32)
+        self._io = _abi.ActuationIO()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_actuation_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        return actuation_fieldnames(self.plan.motor_names)
+
+    @property
+    def power(self) -> torch.Tensor:
+        return self.scalars[0]
+
+    @property
+    def power_average(self) -> torch.Tensor:
+        if not self.plan.has_horizon:
+            raise ValueError("the block has no window: build it with power_horizon")
+        return self.scalars[1]
+
+    @property
+    def reward_power(self) -> torch.Tensor:
+        if self.power_cutoff is None:
+            raise ValueError("the block has no reward: build it with power_cutoff")
+        return self.scalars[2]
+
+    def _launch(self, mode: int, mask: Optional[torch.Tensor]) -> None:
+        eng, io = self._eng, self._io
+
+        def ptr(t: torch.Tensor, dtype=None):
+            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
+                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+            return t.data_ptr()
+        for name in ("q", "v", "a", "command"):
+            setattr(io, name, ptr(eng.field(name)))
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        for name in ("position", "velocity", "acceleration", "bound_low", "bound_high", "scalars"):
+            setattr(io, name, ptr(getattr(self, name)))
+        io.safety = ptr(self.safety, torch.int32) if self.velocity_max is not None else None
+        # (without a horizon the window is not run: rows 1-2 of `scalars` stay zero)
+        io.power_ring = ptr(self.power_ring) if self.plan.has_horizon else None
+        io.power_count = ptr(self.power_count, torch.int32) if self.plan.has_horizon else None
+        self._check(self._L.jm_block_actuation(
+            self._plan, self._dtype, eng.batch_size, self._C.byref(io), mode, int(self.motor_side),
+            self.position_margin if self.position_margin is not None else 0.0,
+            self.velocity_max if self.velocity_max is not None else -1.0, self.power_cutoff or 0.0, eng._stream()))
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """Restart the windows of the masked lanes (every lane without a mask) with the quantities at the state of their new
+        episode; the other lanes keep every tensor, the ring and the counter bit for bit.  Call it after the engine's `start`
+        / `reset_lanes`."""
+        from . import actuation
+        eng = self._eng
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        self._launch(actuation.RESTART, mask)
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream: the quantities at the engine's state, pushed into the window of every lane."""
+        from . import actuation
+        self._launch(actuation.PUSH, None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_actuation_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics and of the locomotion quantities, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities and of the actuated-joint quantities, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "jm_attitude.h"
 #include "jm_frames.h"
 #include "jm_locomotion.h"
+#include "jm_actuation.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -94,6 +95,11 @@ struct jm_frames_plan
 };
 // the locomotion quantities (jm_locomotion.h)
 struct jm_locomotion_plan
+{
+    DevicePlan dev;
+};
+// the actuated-joint quantities (jm_actuation.h)
+struct jm_actuation_plan
 {
     DevicePlan dev;
 };
@@ -347,6 +353,36 @@ int32_t jm_block_locomotion(const jm_locomotion_plan * p, int32_t dtype, int64_t
                               (T *)io->com, (T *)io->vcom, (T *)io->odom_pose, (T *)io->zmp, (T *)io->dcm, (T *)io->h_angular,
                               (T *)io->contact_force_rel, (T *)io->foot_force_vertical, (T *)io->scalars};
         hipLaunchKernelGGL((jm::k_locomotion<T>), grid, dim3(256), 0, s, it, dt, a, momentum_cutoff, friction_cutoff, (long long)B);
+    });
+}
+
+int32_t jm_actuation_plan_create(const jm_actuation_desc * desc, jm_actuation_plan ** out)
+{
+    return plan_create("jm_actuation_plan_create", desc, out, jm::actuation_pack);
+}
+
+int32_t jm_actuation_plan_destroy(jm_actuation_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_actuation(const jm_actuation_plan * p, int32_t dtype, int64_t B, const jm_actuation_io * io, int32_t mode,
+                           int32_t motor_side, double position_margin, double velocity_max, double power_cutoff, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_actuation: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_actuation: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_actuation: bad dtype");
+    if (mode != jm::ACT_RESTART && mode != jm::ACT_PUSH) return fail(JM_EINVAL, "jm_block_actuation: mode must be 0 (restart) or 1 (push)");
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::ActIO<T> a{(const T *)io->q, (const T *)io->v, (const T *)io->a, (const T *)io->command, io->lane_mask,
+                             (T *)io->position, (T *)io->velocity, (T *)io->acceleration, (T *)io->bound_low, (T *)io->bound_high,
+                             io->safety, (T *)io->scalars, (T *)io->power_ring, io->power_count};
+        hipLaunchKernelGGL((jm::k_actuation<T>), grid, dim3(256), 0, s, it, dt, a, (int)mode, (int)motor_side, position_margin,
+                           velocity_max, power_cutoff, (long long)B);
     });
 }
 

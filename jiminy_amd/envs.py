@@ -429,7 +429,8 @@ class WalkerVecEnv(VecJiminyEnv):
 
     def __init__(self, *args: Any, reward_mixture: Optional[Dict[str, float]] = None,
                  frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
-                 locomotion_quantities: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
+                 locomotion_quantities: Optional[Dict[str, Any]] = None, actuated_joints: Optional[Dict[str, Any]] = None,
+                 **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -445,9 +446,18 @@ class WalkerVecEnv(VecJiminyEnv):
         #   impact_force=(max_force_rel, grace_period) ≙ `ImpactForceTermination` (:582-620)
         #   reward_mixture['momentum'] / ['friction']  ≙ `MinimizeAngularMomentumReward` / `MinimizeFrictionReward` (:257-315),
         #                                              weights on the reward rows of the block's `momentum_cutoff` / `friction_cutoff`
-        self.frames = self.locomotion = None
+        # optional `blocks.ActuatedJointQuantities` (its constructor's keywords; `step_dt` is the environment's), reset with the
+        # other two blocks, refreshed once per environment step and exposed as `actuation`; what reads it:
+        #   mechanical_safety=(position_margin, velocity_max, grace_period)  ≙ `MechanicalSafetyTermination`
+        #                                              (compositions/generic.py:505-595): the block's safety count is not zero
+        #   power_consumption=(max_power, grace_period) ≙ `MechanicalPowerConsumptionTermination` (:598-661): the average power
+        #                                              of the block's `power_horizon`, the instantaneous power without one
+        #   reward_mixture['power']                    ≙ `MinimizeMechanicalPowerConsumption` (:153-191), weight on the reward row
+        #                                              of the block's `power_cutoff` and `power_horizon`
+        # one window per block: the reward and the termination share the block's horizon.
+        self.frames = self.locomotion = self.actuation = None
         self._terminations = dict(terminations or {})
-        known = ("base_roll_pitch", "min_base_height", "flying", "impact_force")
+        known = ("base_roll_pitch", "min_base_height", "flying", "impact_force", "mechanical_safety", "power_consumption")
         unknown = set(self._terminations) - set(known)
         if unknown:
             raise ValueError(f"unknown terminations {sorted(unknown)} ({', '.join(known)})")
@@ -462,15 +472,32 @@ class WalkerVecEnv(VecJiminyEnv):
         elif {"momentum", "friction"} & set(self.reward_mixture):
             raise ValueError("the momentum and friction reward terms read the locomotion quantities block: give "
                              "locomotion_quantities as well")
-        if self._terminations and frame_kinematics is None:
+        if {"mechanical_safety", "power_consumption"} & set(self._terminations) and actuated_joints is None:
+            raise ValueError("the mechanical_safety and power_consumption terminations read the actuated-joint quantities "
+                             "block: give actuated_joints as well")
+        if actuated_joints is not None:
+            actuated_joints = dict(actuated_joints)
+            if "power" in self.reward_mixture and (actuated_joints.get("power_cutoff") is None or
+                                                   actuated_joints.get("power_horizon") is None):
+                raise ValueError("reward_mixture['power'] needs actuated_joints['power_cutoff'] and actuated_joints['power_horizon']")
+            if "mechanical_safety" in self._terminations:
+                margin, velocity_max, _ = self._terminations["mechanical_safety"]
+                given = (actuated_joints.setdefault("position_margin", margin), actuated_joints.setdefault("velocity_max", velocity_max))
+                if given != (margin, velocity_max):
+                    raise ValueError("the mechanical_safety termination and actuated_joints give different position_margin / "
+                                     "velocity_max: the block evaluates one pair")
+        elif "power" in self.reward_mixture:
+            raise ValueError("the power reward term reads the actuated-joint quantities block: give actuated_joints as well")
+        if set(self._terminations) - {"mechanical_safety", "power_consumption"} and frame_kinematics is None:
             raise ValueError("the terminations read the frame kinematics block: give frame_kinematics as well")
         if frame_kinematics is not None:
-            names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, self._terminations, locomotion_quantities)
+            reading = {k: v for k, v in self._terminations.items() if k not in ("mechanical_safety", "power_consumption")}
+            names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities)
             self.frames = blocks.FrameKinematics(self.engine, names, reference_frames=modes, **cfg)
             if locomotion_quantities is not None:
                 self.engine.enable_output("centroidal")
                 self.locomotion = blocks.LocomotionQuantities(self.engine, self.frames, **locomotion_quantities)
-            if self._terminations:
+            if set(self._terminations) - {"mechanical_safety", "power_consumption"}:
                 self._frame_root = self.frames.index("root_joint")
                 self._frame_contacts = torch.tensor([self.frames.index(n) for n in self.model.contacts], dtype=torch.long, device=self.device)
                 if "base_roll_pitch" in self._terminations:
@@ -480,6 +507,8 @@ class WalkerVecEnv(VecJiminyEnv):
                     self._roll_pitch_bounds = (bound(low), bound(high), float(grace))
                 if "min_base_height" in self._terminations and not self.model.contacts:
                     raise ValueError("min_base_height needs a model with contact frames")
+        if actuated_joints is not None:
+            self.actuation = blocks.ActuatedJointQuantities(self.engine, step_dt=self.step_dt, **actuated_joints)
         m = self.model
         lim = torch.tensor([mo.effort_limit * mo.velocity_limit for mo in m.motors], dtype=self.dtype)
         self._power_consumption_max = float(lim.sum())  # locomotion.py:230-236
@@ -535,6 +564,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(None)
         if self.locomotion is not None:
             self.locomotion.reset(None)
+        if self.actuation is not None:
+            self.actuation.reset(None)
         return out
 
     def reset_lanes(self, lane_mask: torch.Tensor) -> None:
@@ -544,6 +575,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(lane_mask)
         if self.locomotion is not None:
             self.locomotion.reset(lane_mask)
+        if self.actuation is not None:
+            self.actuation.reset(lane_mask)
 
     def _after_step(self):
         self._dir_sum += self.engine.robot_state.q[1].to(torch.float64)
@@ -554,6 +587,8 @@ class WalkerVecEnv(VecJiminyEnv):
                 self.frames.refresh_average(self.step_dt)
         if self.locomotion is not None:
             self.locomotion.refresh()
+        if self.actuation is not None:
+            self.actuation.refresh()
         return super()._after_step()
 
     def base_relative_height(self) -> torch.Tensor:
@@ -583,6 +618,14 @@ class WalkerVecEnv(VecJiminyEnv):
             if "impact_force" in self._terminations:
                 max_force_rel, grace = self._terminations["impact_force"]
                 terminated = terminated | ((t >= grace) & (self.locomotion.force_vertical_max > max_force_rel))
+            if "mechanical_safety" in self._terminations:
+                grace = self._terminations["mechanical_safety"][2]
+                terminated = terminated | ((t >= grace) & (self.actuation.safety > 0))
+            if "power_consumption" in self._terminations:
+                max_power, grace = self._terminations["power_consumption"]
+                act = self.actuation
+                value = act.power_average if act.plan.has_horizon else act.power      # (compositions/generic.py:640-650)
+                terminated = terminated | ((t >= grace) & (value > max_power))
         return terminated, truncated
 
     def compute_reward(self, terminated: torch.Tensor) -> torch.Tensor:
@@ -605,6 +648,8 @@ class WalkerVecEnv(VecJiminyEnv):
             total += self.reward_mixture["momentum"] * self.locomotion.reward_momentum
         if "friction" in self.reward_mixture:
             total += self.reward_mixture["friction"] * self.locomotion.reward_friction
+        if "power" in self.reward_mixture:
+            total += self.reward_mixture["power"] * self.actuation.reward_power
         return total
 
 
@@ -826,6 +871,9 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
             if whole_step and self.frames is not None:
                 raise NotImplementedError("whole-step graphs do not take the frame kinematics block: its reset is not part "
                                           "of the captured step")
+            if whole_step and self.actuation is not None:
+                raise NotImplementedError("whole-step graphs do not take the actuated-joint quantities block: the restart of "
+                                          "its windows at reset is not part of the captured step")
             if whole_step and self._mahony is not None:
                 raise NotImplementedError("whole-step graphs do not take the MahonyFilter / BodyObserver blocks: their "
                                           "initialisation at reset is not part of the captured step")
