@@ -843,6 +843,62 @@ int32_t jm_block_actuation(const jm_actuation_plan * plan, int32_t dtype, int64_
                            int32_t mode, int32_t motor_side, double position_margin, double velocity_max, double power_cutoff,
                            void * stream);
 
+/* ---- Foot pose quantities: the mean pose of the feet of a legged robot, its odometry pose, the pose of every foot but the
+ * last relative to the mean, and the tracking error and rewards against a reference of the relative poses; batched, one
+ * lane = one environment, one launch per refresh.  New symbols only: no existing structure or signature changed with them.
+ * Reference: python/gym_jiminy/common/gym_jiminy/common/quantities/generic.py:950-1062, quantities/locomotion.py:416-557 and
+ * :683-810, compositions/generic.py:64-122, compositions/locomotion.py:146-214, restated operation for operation.
+ * jm_footposes_desc: the plan (host array, copied by jm_footposes_plan_create).  `n_frames` = K, the number of columns of the
+ *   `pose` tensor of the frame kinematics block (its row stride is `n_frames * B`); per foot, in the order of
+ *   `sanitize_foot_frame_names` (quantities/locomotion.py:31-84: sorted names), the column of its frame (`foot_column`).
+ *   jm_footposes_plan_create validates the description (JM_EINVAL + jm_last_error, before any device call: null array,
+ *   1 <= n_feet <= 64, n_feet <= n_frames, columns inside [0, n_frames), no column twice) and uploads it; the launch then
+ *   allocates, copies and synchronises nothing.
+ * jm_footposes_io: the device pointers of one launch, arrays `[rows][B]` of the scalar type `dtype`, F = n_feet.  Every
+ *   pointer may be NULL: the outputs that need it are then not written.  Inputs: `pose` `[7][K][B]` (x y z, quaternion xyzw);
+ *   `reference_relative_pose` `[7][F - 1][B]`, the reference value of `relative_pose` (what `QuantityEvalMode.REFERENCE` gives
+ *   the reference's tracking rewards); `lane_mask` (uint8 `[B]`, NULL: every lane; other lanes are not touched).  Outputs:
+ *     mean_pose[7]             `MultiFootMeanXYZQuat` (quantities/locomotion.py:416-478) = `MultiFrameMeanXYZQuat.refresh`
+ *                              (quantities/generic.py:1055-1062): `position_average` and `quat_average_2d` (:950-980) -- one
+ *                              foot: a copy; two: `quat_interpolate_middle` (utils/math.py:1296-1331); three or more: the
+ *                              eigenvector of the largest eigenvalue of sum q q^T, with a non-negative dot product with the
+ *                              first foot's quaternion (LAPACK's sign, which the reference inherits, is arbitrary)
+ *     mean_odom_pose[3]        `MultiFootMeanOdometryPose` (quantities/locomotion.py:482-557): x, y of the mean, `quat_to_yaw`
+ *                              (utils/math.py:95-141) of its quaternion
+ *     relative_pose[7][F - 1]  `MultiFootRelativeXYZQuat.refresh` (:779-810): R_mean^T (p_i - p_mean) (`quat_to_matrix`,
+ *                              utils/math.py:214-248; `translate_positions`, :683-698) and conj(q_mean) q_i (`quat_multiply`,
+ *                              utils/math.py:570-626), the last foot dropped
+ *     tracking_error[6][F - 1] with a reference only: rows 0-2 relative position - reference position, rows 3-5
+ *                              `quat_difference(relative quaternion, reference quaternion)` (utils/math.py:971-1005, `log3`
+ *                              :724-774): the errors `TrackingQuantityReward` (compositions/generic.py:64-122) feeds its kernel
+ *     scalars[2]               0 reward_foot_positions = `radial_basis_function(rows 0-2, position_cutoff, 2)`
+ *                              (`TrackingFootPositionsReward`, compositions/locomotion.py:146-176; compositions/mixin.py:17-66,
+ *                              CUTOFF_ESP = 1e-2); 1 reward_foot_orientations = the same of rows 3-5 with `orientation_cutoff`
+ *                              (`TrackingFootOrientationsReward`, :179-214).  A non-positive cutoff: that row is not written;
+ *                              without a reference neither is, unless F = 1, where the error is empty and both are 1. */
+typedef struct jm_footposes_desc
+{
+    int32_t n_frames;
+    int32_t n_feet;
+    const int32_t * foot_column;        /* [n_feet] */
+} jm_footposes_desc;
+typedef struct jm_footposes_io
+{
+    const void * pose;
+    const void * reference_relative_pose;
+    const uint8_t * lane_mask;
+    void * mean_pose;
+    void * mean_odom_pose;
+    void * relative_pose;
+    void * tracking_error;
+    void * scalars;
+} jm_footposes_io;
+typedef struct jm_footposes_plan jm_footposes_plan;
+int32_t jm_footposes_plan_create(const jm_footposes_desc * desc, jm_footposes_plan ** out);
+int32_t jm_footposes_plan_destroy(jm_footposes_plan * plan);
+int32_t jm_block_foot_poses(const jm_footposes_plan * plan, int32_t dtype, int64_t batch_size, const jm_footposes_io * io,
+                            double position_cutoff, double orientation_cutoff, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

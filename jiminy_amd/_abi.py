@@ -145,6 +145,20 @@ class ActuationIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ACTUATION_IO_FIELDS]
 
 
+class FootPosesDesc(C.Structure):
+    """jm_footposes_desc: the plan of the foot pose quantities (jiminy_amd.footposes builds it)."""
+    _fields_ = [("n_frames", C.c_int32), ("n_feet", C.c_int32), ("foot_column", _pi)]
+
+
+FOOTPOSES_IO_FIELDS = ("pose", "reference_relative_pose", "lane_mask", "mean_pose", "mean_odom_pose", "relative_pose",
+                       "tracking_error", "scalars")
+
+
+class FootPosesIO(C.Structure):
+    """jm_footposes_io: the device pointers of one launch of jm_block_foot_poses, each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in FOOTPOSES_IO_FIELDS]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

@@ -37,6 +37,11 @@ jiminy_amd/locomotion.py builds; specification: tests/golden/ref_locomotion.npz.
 the mechanical stops, the mechanical-safety count, the mechanical power, its sliding average over environment steps and the
 reward on it) from the engine's `q / v / a / command`: one HIP launch per refresh (csrc/jm_actuation.h) driven by a plan that
 jiminy_amd/actuation.py builds; specification: tests/golden/ref_actuation.npz.
+
+`FootPoseQuantities` gives the mean pose of the feet (position mean and quaternion average: a copy, a midpoint or the dominant
+eigenvector of a 4 x 4 matrix per lane), its odometry pose, the poses of the feet relative to it and the tracking error and
+rewards against a reference of those relative poses, from the `pose` of a `FrameKinematics`: one HIP launch per refresh
+(csrc/jm_footposes.h) driven by a plan that jiminy_amd/footposes.py builds; specification: tests/golden/ref_footposes.npz.
 """
 from __future__ import annotations
 
@@ -790,6 +795,141 @@ class ActuatedJointQuantities:
         if plan:
             try:
                 self._L.jm_actuation_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+FOOTPOSES_SCALARS = ("reward_foot_positions", "reward_foot_orientations")
+
+
+def footposes_fieldnames(foot_frame_names):
+    """Names of the rows of the tensors of a `FootPoseQuantities` block (`[row][foot]` for the relative ones)."""
+    pose = ("X", "Y", "Z", "QuatX", "QuatY", "QuatZ", "QuatW")
+    rel = list(foot_frame_names)[:-1]
+    return {"mean_pose": [f"FootMean.{e}" for e in pose], "mean_odom_pose": ["FootMeanOdom.X", "FootMeanOdom.Y", "FootMeanOdom.Yaw"],
+            "relative_pose": [[f"{n}.Relative{e}" for n in rel] for e in pose],
+            "reference_relative_pose": [[f"{n}.ReferenceRelative{e}" for n in rel] for e in pose],
+            "tracking_error": [[f"{n}.Error{e}" for n in rel] for e in ("X", "Y", "Z", "AngX", "AngY", "AngZ")],
+            "scalars": list(FOOTPOSES_SCALARS)}
+
+
+class FootPoseQuantities:
+    """The foot pose quantities of the reference's locomotion layer per lane, from the `pose` of a `FrameKinematics`, F feet in
+    the order of `foot_frame_names` (sorted, `sanitize_foot_frame_names`): `mean_pose` `[7][B]` ≙ `MultiFootMeanXYZQuat`
+    (quantities/locomotion.py:416-478; quantities/generic.py:950-1062); `mean_odom_pose` `[3][B]` ≙ `MultiFootMeanOdometryPose`
+    (:482-557); `relative_pose` `[7][F-1][B]` ≙ `MultiFootRelativeXYZQuat` (:702-810), the pose of every foot but the last in
+    the mean pose; `tracking_error` `[6][F-1][B]`: relative position minus reference position and
+    `quat_difference(relative quaternion, reference quaternion)`, the errors of `TrackingFootPositionsReward` /
+    `TrackingFootOrientationsReward` (compositions/locomotion.py:146-214); `scalars` `[2][B]`, rows `FOOTPOSES_SCALARS`: those two
+    rewards with `position_cutoff` / `orientation_cutoff` (None: that row stays zero and its property raises).
+
+    The reference is `reference_relative_pose` `[7][F-1][B]`, a tensor of the block the caller fills (it stands for what
+    `QuantityEvalMode.REFERENCE` reads from a trajectory database): zero positions and unit quaternions at first;
+    `set_reference_from_current(lane_mask)` copies `relative_pose` into it on the masked lanes.
+
+    Deviation: with three feet or more the mean quaternion is an eigenvector, whose sign LAPACK leaves arbitrary in the
+    reference; here it has a non-negative dot product with the quaternion of the first foot.  Yaw, error and rewards do not
+    depend on the sign; the relative quaternions flip with it.
+
+    `frames`: the `FrameKinematics` block of the same engine, holding every foot frame; refresh it first.  `refresh()` is one
+    launch on the engine's stream, without allocation, copy or synchronisation; `reset(lane_mask)` evaluates the masked lanes
+    (every lane without a mask) and keeps the others bit for bit.  The tensors never change identity."""
+
+    def __init__(self, engine, frames: "FrameKinematics", *, foot_frame_names="auto", position_cutoff: Optional[float] = None,
+                 orientation_cutoff: Optional[float] = None) -> None:
+        import ctypes as C
+
+        from . import _abi, footposes
+        if not engine.model.has_freeflyer:
+            raise ValueError("Only legged robot with floating base are supported: the model has no free-flyer.")
+        if frames._eng is not engine:
+            raise ValueError("the frame kinematics block belongs to another engine")
+        for cutoff in (position_cutoff, orientation_cutoff):
+            if cutoff is not None and not float(cutoff) > 0.0:
+                raise ValueError("a reward cutoff must be positive")
+        self.plan = footposes.build_plan(engine.model, frames.frame_names, foot_frame_names)
+        self._C = C
+        self._eng, self._frames = engine, frames
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.foot_frame_names = list(self.plan.foot_frame_names)
+        self.position_cutoff = None if position_cutoff is None else float(position_cutoff)
+        self.orientation_cutoff = None if orientation_cutoff is None else float(orientation_cutoff)
+        B, R = engine.batch_size, self.plan.n_feet - 1
+        new = lambda *shape: torch.zeros((*shape, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
+        self.mean_pose, self.mean_odom_pose, self.scalars = new(7), new(3), new(2)
+        self.relative_pose, self.reference_relative_pose, self.tracking_error = new(7, R), new(7, R), new(6, R)
+        for t in (self.mean_pose, self.relative_pose, self.reference_relative_pose):
+            t[6] = 1.0
+        self._io = _abi.FootPosesIO()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_footposes_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        return footposes_fieldnames(self.foot_frame_names)
+
+    @property
+    def reward_foot_positions(self) -> torch.Tensor:
+        if self.position_cutoff is None:
+            raise ValueError("the block has no position reward: build it with position_cutoff")
+        return self.scalars[0]
+
+    @property
+    def reward_foot_orientations(self) -> torch.Tensor:
+        if self.orientation_cutoff is None:
+            raise ValueError("the block has no orientation reward: build it with orientation_cutoff")
+        return self.scalars[1]
+
+    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        if lane_mask is None:
+            return None
+        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
+        if tuple(mask.shape) != (self._eng.batch_size,):
+            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
+        return mask
+
+    def _launch(self, mask: Optional[torch.Tensor]) -> None:
+        eng, io = self._eng, self._io
+
+        def ptr(t: torch.Tensor):
+            if not t.is_contiguous() or t.device != eng.device or t.dtype != eng.dtype:
+                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+            return t.data_ptr() if t.numel() else None        # (one foot: the relative tensors have no column)
+        io.pose = ptr(self._frames.pose)
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        for name in ("reference_relative_pose", "mean_pose", "mean_odom_pose", "relative_pose", "tracking_error", "scalars"):
+            setattr(io, name, ptr(getattr(self, name)))
+        self._check(self._L.jm_block_foot_poses(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
+                                                self.position_cutoff or 0.0, self.orientation_cutoff or 0.0, eng._stream()))
+
+    def set_reference_from_current(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """`relative_pose` becomes the reference of the masked lanes (every lane without a mask); the tracking error and the
+        rewards follow at the next `refresh` / `reset`."""
+        mask = self._mask(lane_mask)
+        if mask is None:
+            self.reference_relative_pose.copy_(self.relative_pose)
+        else:
+            torch.where(mask.bool(), self.relative_pose, self.reference_relative_pose, out=self.reference_relative_pose)
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The quantities at the state of a new episode on the masked lanes (every lane without a mask); the other lanes
+        keep every tensor bit for bit.  Call it after the engine's `start` / `reset_lanes` and the reset of `frames`."""
+        self._launch(self._mask(lane_mask))
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream, behind the refresh of `frames`."""
+        self._launch(None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_footposes_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities and of the actuated-joint quantities, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities and of the foot pose quantities, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include "jm_frames.h"
 #include "jm_locomotion.h"
 #include "jm_actuation.h"
+#include "jm_footposes.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -100,6 +101,11 @@ struct jm_locomotion_plan
 };
 // the actuated-joint quantities (jm_actuation.h)
 struct jm_actuation_plan
+{
+    DevicePlan dev;
+};
+// the foot pose quantities (jm_footposes.h)
+struct jm_footposes_plan
 {
     DevicePlan dev;
 };
@@ -383,6 +389,33 @@ int32_t jm_block_actuation(const jm_actuation_plan * p, int32_t dtype, int64_t B
                              io->safety, (T *)io->scalars, (T *)io->power_ring, io->power_count};
         hipLaunchKernelGGL((jm::k_actuation<T>), grid, dim3(256), 0, s, it, dt, a, (int)mode, (int)motor_side, position_margin,
                            velocity_max, power_cutoff, (long long)B);
+    });
+}
+
+int32_t jm_footposes_plan_create(const jm_footposes_desc * desc, jm_footposes_plan ** out)
+{
+    return plan_create("jm_footposes_plan_create", desc, out, jm::footposes_pack);
+}
+
+int32_t jm_footposes_plan_destroy(jm_footposes_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_foot_poses(const jm_footposes_plan * p, int32_t dtype, int64_t B, const jm_footposes_io * io, double position_cutoff,
+                            double orientation_cutoff, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_foot_poses: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_foot_poses: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_foot_poses: bad dtype");
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::FootIO<T> a{(const T *)io->pose, (const T *)io->reference_relative_pose, io->lane_mask, (T *)io->mean_pose,
+                              (T *)io->mean_odom_pose, (T *)io->relative_pose, (T *)io->tracking_error, (T *)io->scalars};
+        hipLaunchKernelGGL((jm::k_foot_poses<T>), grid, dim3(256), 0, s, it, dt, a, position_cutoff, orientation_cutoff, (long long)B);
     });
 }
 

@@ -430,7 +430,7 @@ class WalkerVecEnv(VecJiminyEnv):
     def __init__(self, *args: Any, reward_mixture: Optional[Dict[str, float]] = None,
                  frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
                  locomotion_quantities: Optional[Dict[str, Any]] = None, actuated_joints: Optional[Dict[str, Any]] = None,
-                 **kw: Any) -> None:
+                 foot_poses: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -455,7 +455,13 @@ class WalkerVecEnv(VecJiminyEnv):
         #   reward_mixture['power']                    ≙ `MinimizeMechanicalPowerConsumption` (:153-191), weight on the reward row
         #                                              of the block's `power_cutoff` and `power_horizon`
         # one window per block: the reward and the termination share the block's horizon.
-        self.frames = self.locomotion = self.actuation = None
+        # optional `blocks.FootPoseQuantities` (its constructor's keywords), reset and refreshed behind the frames block like
+        # `locomotion` and exposed as `foot_poses`; the reference of its relative poses is the block's tensor, which the caller
+        # fills (`set_reference_from_current`); what reads it:
+        #   reward_mixture['foot_positions'] / ['foot_orientations']  ≙ `TrackingFootPositionsReward` /
+        #                                              `TrackingFootOrientationsReward` (compositions/locomotion.py:146-214), weights
+        #                                              on the reward rows of the block's `position_cutoff` / `orientation_cutoff`
+        self.frames = self.locomotion = self.actuation = self.foot_poses = None
         self._terminations = dict(terminations or {})
         known = ("base_roll_pitch", "min_base_height", "flying", "impact_force", "mechanical_safety", "power_consumption")
         unknown = set(self._terminations) - set(known)
@@ -488,12 +494,25 @@ class WalkerVecEnv(VecJiminyEnv):
                                      "velocity_max: the block evaluates one pair")
         elif "power" in self.reward_mixture:
             raise ValueError("the power reward term reads the actuated-joint quantities block: give actuated_joints as well")
+        if foot_poses is not None:
+            frame_kinematics = {} if frame_kinematics is None else frame_kinematics
+            for term, cutoff in (("foot_positions", "position_cutoff"), ("foot_orientations", "orientation_cutoff")):
+                if term in self.reward_mixture and foot_poses.get(cutoff) is None:
+                    raise ValueError(f"reward_mixture['{term}'] needs foot_poses['{cutoff}']")
+        elif {"foot_positions", "foot_orientations"} & set(self.reward_mixture):
+            raise ValueError("the foot_positions and foot_orientations reward terms read the foot pose quantities block: give "
+                             "foot_poses as well")
         if set(self._terminations) - {"mechanical_safety", "power_consumption"} and frame_kinematics is None:
             raise ValueError("the terminations read the frame kinematics block: give frame_kinematics as well")
         if frame_kinematics is not None:
             reading = {k: v for k, v in self._terminations.items() if k not in ("mechanical_safety", "power_consumption")}
-            names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities)
+            if foot_poses is None:
+                names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities)
+            else:
+                names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities, foot_poses)
             self.frames = blocks.FrameKinematics(self.engine, names, reference_frames=modes, **cfg)
+            if foot_poses is not None:
+                self.foot_poses = blocks.FootPoseQuantities(self.engine, self.frames, **foot_poses)
             if locomotion_quantities is not None:
                 self.engine.enable_output("centroidal")
                 self.locomotion = blocks.LocomotionQuantities(self.engine, self.frames, **locomotion_quantities)
@@ -525,11 +544,12 @@ class WalkerVecEnv(VecJiminyEnv):
 
     @staticmethod
     def frame_kinematics_config(model: CompiledModel, frame_kinematics: Dict[str, Any], terminations: Dict[str, Any],
-                                locomotion_quantities: Optional[Dict[str, Any]] = None
-                                ) -> Tuple[list, Optional[list], Dict[str, Any]]:
+                                locomotion_quantities: Optional[Dict[str, Any]] = None,
+                                foot_poses: Optional[Dict[str, Any]] = None) -> Tuple[list, Optional[list], Dict[str, Any]]:
         """Frame names, reference frames and remaining keywords of the `blocks.FrameKinematics` of an environment: the
         user's, plus what the terminations and the locomotion quantities read where it is missing -- the root joint and
-        every contact frame (LOCAL), the Euler angles for `base_roll_pitch` and the step average for the angular momentum."""
+        every contact frame (LOCAL), the Euler angles for `base_roll_pitch` and the step average for the angular momentum; with
+        `foot_poses` (the keywords of the foot pose quantities block) the foot frames (LOCAL) as well."""
         cfg = dict(frame_kinematics)
         names = list(cfg.pop("frame_names", ()))
         modes = cfg.pop("reference_frames", None)
@@ -546,6 +566,13 @@ class WalkerVecEnv(VecJiminyEnv):
                 cfg["compute_rpy"] = True
             if locomotion_quantities is not None and locomotion_quantities.get("momentum", True):
                 cfg["average"] = True
+        if foot_poses is not None:
+            from .locomotion import sanitize_foot_frame_names
+            for name in sanitize_foot_frame_names(model, foot_poses.get("foot_frame_names", "auto")):
+                if name not in names:
+                    names.append(name)
+                    if modes is not None:
+                        modes.append("LOCAL")
         return names, modes, cfg
 
     def _direction_restart(self, lane_mask: Optional[torch.Tensor]) -> None:
@@ -564,6 +591,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(None)
         if self.locomotion is not None:
             self.locomotion.reset(None)
+        if self.foot_poses is not None:
+            self.foot_poses.reset(None)
         if self.actuation is not None:
             self.actuation.reset(None)
         return out
@@ -575,6 +604,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(lane_mask)
         if self.locomotion is not None:
             self.locomotion.reset(lane_mask)
+        if self.foot_poses is not None:
+            self.foot_poses.reset(lane_mask)
         if self.actuation is not None:
             self.actuation.reset(lane_mask)
 
@@ -587,6 +618,8 @@ class WalkerVecEnv(VecJiminyEnv):
                 self.frames.refresh_average(self.step_dt)
         if self.locomotion is not None:
             self.locomotion.refresh()
+        if self.foot_poses is not None:
+            self.foot_poses.refresh()
         if self.actuation is not None:
             self.actuation.refresh()
         return super()._after_step()
@@ -650,6 +683,10 @@ class WalkerVecEnv(VecJiminyEnv):
             total += self.reward_mixture["friction"] * self.locomotion.reward_friction
         if "power" in self.reward_mixture:
             total += self.reward_mixture["power"] * self.actuation.reward_power
+        if "foot_positions" in self.reward_mixture:
+            total += self.reward_mixture["foot_positions"] * self.foot_poses.reward_foot_positions
+        if "foot_orientations" in self.reward_mixture:
+            total += self.reward_mixture["foot_orientations"] * self.foot_poses.reward_foot_orientations
         return total
 
 
