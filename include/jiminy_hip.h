@@ -899,6 +899,80 @@ int32_t jm_footposes_plan_destroy(jm_footposes_plan * plan);
 int32_t jm_block_foot_poses(const jm_footposes_plan * plan, int32_t dtype, int64_t batch_size, const jm_footposes_io * io,
                             double position_cutoff, double orientation_cutoff, void * stream);
 
+/* ---- Tracking windows: the drift of the base odometry pose and the shift of the relative foot poses and of the motor
+ * positions against a reference motion, each over a sliding window of environment steps; batched, one lane = one
+ * environment, one launch per refresh.  New symbols only: no existing structure or signature changed with them.  Reference:
+ * python/gym_jiminy/common/gym_jiminy/common/quantities/transform.py:208-296 (`StackedQuantity.refresh`, both branches) and
+ * :715-831 (`DeltaQuantity`), quantities/locomotion.py:1537-1693, compositions/generic.py:194-453 and :664-716,
+ * compositions/locomotion.py:76-120 and :623-867, restated operation for operation.
+ * jm_tracking_desc: the plan.  One window length per family, `max(ceil(horizon / step_dt), 1) + 1` (compositions/generic.py:430,
+ *   quantities/locomotion.py:1573), 0: the family is absent; `n_rel` = F - 1, the columns of the relative foot poses; `n_motors`
+ *   the rows of the motor positions.  jm_tracking_plan_create validates the description (JM_EINVAL + jm_last_error, before any
+ *   device call: 2 <= each max_stack <= 1024, 1 <= n_rel <= 63, 1 <= n_motors <= 256, the sizes of an absent family 0, at least
+ *   one family) and uploads it; the launch then allocates, copies and synchronises nothing.
+ * jm_tracking_io: the device pointers of one launch, arrays `[rows][B]` of the scalar type `dtype` but the two integer ones.
+ *   Every pointer may be NULL: a family one of whose inputs or state arrays is NULL is skipped, an output that is NULL is not
+ *   written; without `count` nothing runs.  Inputs: `odom_pose`, `reference_odom_pose` `[3][B]` (x, y, yaw: `BaseOdometryPose`);
+ *   `relative_pose`, `reference_relative_pose` `[7][n_rel][B]` (`MultiFootRelativeXYZQuat`); `position`, `reference_position`
+ *   `[n_motors][B]` (`MultiActuatedJointKinematic`, joint side); `lane_mask` (uint8 `[B]`, NULL: every lane; other lanes are
+ *   not touched).  State, owned by the caller: `count` (int32 `[B]`, the `num_steps` of the reference's stacks per lane, shared
+ *   by the families); `odom_ring` `[max_stack_odom][4][B]` (true x, true y, reference x, reference y), `yaw_prev` `[2][B]`,
+ *   `yaw_ring` `[max_stack_odom - 1][2][B]` (true, reference); `foot_ring` `[2][max_stack_foot][B]`; `motor_ring`
+ *   `[max_stack_motor][B]`.  Outputs:
+ *     delta_odom, delta_odom_reference [3]   `DeltaBaseOdometryPosition` (quantities/locomotion.py:1537-1599: newest - oldest
+ *                              value of the window, `DeltaQuantity` with bounds_only=True) and `DeltaBaseOdometryOrientation`
+ *                              (:1630-1693: the sum over the window of `angle_difference` (:1602-1627) between successive steps,
+ *                              bounds_only=False, so that turns are counted), of the true and of the reference pose
+ *     scalars[6]               0 drift_odom_position = |dxy_true - dxy_ref|, 1 drift_odom_orientation = |dyaw_true - dyaw_ref|
+ *                              (`compute_drift_error`, compositions/generic.py:194-208;
+ *                              `DriftTrackingBaseOdometryPositionTermination` / `...OrientationTermination`,
+ *                              compositions/locomotion.py:623-736); 2 reward_odom_pose = `radial_basis_function([|dxy_true| -
+ *                              |dxy_ref|, dyaw_true - dyaw_ref], odometry_cutoff, 2)` (`DriftTrackingBaseOdometryPoseReward`,
+ *                              :85-120; a non-positive cutoff: not written); 3 shift_foot_positions, 4
+ *                              shift_foot_orientations: `min_norm` (compositions/generic.py:318-330) over the window of the
+ *                              difference of rows 0-1, and of `angle_distance` (compositions/locomotion.py:794-810) of the
+ *                              `quat_to_yaw` (utils/math.py:95-141) of rows 3-6, of the relative foot poses
+ *                              (`ShiftTrackingFootOdometryPositionsTermination` / `...OrientationsTermination`, :739-867); 5
+ *                              shift_motor_positions: `min_norm` of position - reference
+ *                              (`ShiftTrackingMotorPositionsTermination`, compositions/generic.py:664-716).  The rings of the
+ *                              two shift families hold one sum of squares per timestamp, which `min_norm` reduces.  NaN
+ *                              propagates like `np.min` and `np.sum`.
+ * jm_block_tracking: `mode` 0 restarts the windows of the launched lanes (count = 0: what the first refresh of an episode
+ *   gives), `mode` 1 pushes one environment step (count += 1).  No argument changes from step to step, so the launch can be part
+ *   of a captured graph. */
+typedef struct jm_tracking_desc
+{
+    int32_t max_stack_odom;
+    int32_t max_stack_foot;
+    int32_t max_stack_motor;
+    int32_t n_rel;
+    int32_t n_motors;
+} jm_tracking_desc;
+typedef struct jm_tracking_io
+{
+    const void * odom_pose;
+    const void * reference_odom_pose;
+    const void * relative_pose;
+    const void * reference_relative_pose;
+    const void * position;
+    const void * reference_position;
+    const uint8_t * lane_mask;
+    int32_t * count;
+    void * odom_ring;
+    void * yaw_prev;
+    void * yaw_ring;
+    void * foot_ring;
+    void * motor_ring;
+    void * delta_odom;
+    void * delta_odom_reference;
+    void * scalars;
+} jm_tracking_io;
+typedef struct jm_tracking_plan jm_tracking_plan;
+int32_t jm_tracking_plan_create(const jm_tracking_desc * desc, jm_tracking_plan ** out);
+int32_t jm_tracking_plan_destroy(jm_tracking_plan * plan);
+int32_t jm_block_tracking(const jm_tracking_plan * plan, int32_t dtype, int64_t batch_size, const jm_tracking_io * io, int32_t mode,
+                          double odometry_cutoff, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

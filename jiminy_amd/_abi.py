@@ -159,6 +159,22 @@ class FootPosesIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in FOOTPOSES_IO_FIELDS]
 
 
+class TrackingDesc(C.Structure):
+    """jm_tracking_desc: the plan of the tracking windows (jiminy_amd.tracking builds it)."""
+    _fields_ = [("max_stack_odom", C.c_int32), ("max_stack_foot", C.c_int32), ("max_stack_motor", C.c_int32), ("n_rel", C.c_int32),
+                ("n_motors", C.c_int32)]
+
+
+TRACKING_IO_FIELDS = ("odom_pose", "reference_odom_pose", "relative_pose", "reference_relative_pose", "position",
+                      "reference_position", "lane_mask", "count", "odom_ring", "yaw_prev", "yaw_ring", "foot_ring", "motor_ring",
+                      "delta_odom", "delta_odom_reference", "scalars")
+
+
+class TrackingIO(C.Structure):
+    """jm_tracking_io: the device pointers of one launch of jm_block_tracking, each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in TRACKING_IO_FIELDS]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

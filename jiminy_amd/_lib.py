@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "jm_locomotion_plan_create", "jm_locomotion_plan_destroy", "jm_block_locomotion",
     "jm_actuation_plan_create", "jm_actuation_plan_destroy", "jm_block_actuation",
     "jm_footposes_plan_create", "jm_footposes_plan_destroy", "jm_block_foot_poses",
+    "jm_tracking_plan_create", "jm_tracking_plan_destroy", "jm_block_tracking",
 )
 
 
@@ -132,6 +133,9 @@ class HipLibrary:
         L.jm_footposes_plan_create.argtypes = [C.POINTER(_abi.FootPosesDesc), C.POINTER(vp)]
         L.jm_footposes_plan_destroy.argtypes = [vp]
         L.jm_block_foot_poses.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.FootPosesIO), C.c_double, C.c_double, vp]
+        L.jm_tracking_plan_create.argtypes = [C.POINTER(_abi.TrackingDesc), C.POINTER(vp)]
+        L.jm_tracking_plan_destroy.argtypes = [vp]
+        L.jm_block_tracking.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrackingIO), C.c_int32, C.c_double, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

@@ -42,6 +42,11 @@ jiminy_amd/actuation.py builds; specification: tests/golden/ref_actuation.npz.
 eigenvector of a 4 x 4 matrix per lane), its odometry pose, the poses of the feet relative to it and the tracking error and
 rewards against a reference of those relative poses, from the `pose` of a `FrameKinematics`: one HIP launch per refresh
 (csrc/jm_footposes.h) driven by a plan that jiminy_amd/footposes.py builds; specification: tests/golden/ref_footposes.npz.
+
+`TrackingWindows` gives the drift of the odometry pose and the shift of the relative foot poses and of the motor positions
+against a reference motion over sliding windows of environment steps, and the reward on the drift, from the tensors of the
+three blocks above: one HIP launch per refresh (csrc/jm_tracking.h) driven by a plan that jiminy_amd/tracking.py builds;
+specification: tests/golden/ref_tracking.npz.
 """
 from __future__ import annotations
 
@@ -930,6 +935,207 @@ class FootPoseQuantities:
         if plan:
             try:
                 self._L.jm_footposes_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+def tracking_fieldnames(foot_frame_names, motor_names):
+    """Names of the rows of the tensors of a `TrackingWindows` block (`[row][foot]` for the foot reference)."""
+    from .tracking import SCALARS
+    odom = ("X", "Y", "Yaw")
+    return {"reference_odom_pose": [f"ReferenceOdom.{e}" for e in odom], "delta_odom": [f"DeltaOdom.{e}" for e in odom],
+            "delta_odom_reference": [f"ReferenceDeltaOdom.{e}" for e in odom],
+            "reference_relative_pose": footposes_fieldnames(foot_frame_names)["reference_relative_pose"] if foot_frame_names else [],
+            "reference_position": [f"{n}.ReferencePosition" for n in motor_names], "scalars": list(SCALARS)}
+
+
+class TrackingWindows:
+    """The trajectory-tracking windows of the reference's composition layer per lane, over sliding windows of environment
+    steps: `delta_odom`, `delta_odom_reference` `[3][B]` ≙ `DeltaBaseOdometryPosition` / `DeltaBaseOdometryOrientation`
+    (quantities/locomotion.py:1537-1693) of the true and of the reference odometry pose; `scalars` `[6][B]`, rows
+    `tracking.SCALARS`: `drift_odom_position`, `drift_odom_orientation` ≙ the values of
+    `DriftTrackingBaseOdometryPositionTermination` / `...OrientationTermination` (compositions/locomotion.py:623-736),
+    `reward_odom_pose` ≙ `DriftTrackingBaseOdometryPoseReward` (:85-120) with `odometry_cutoff`, `shift_foot_positions`,
+    `shift_foot_orientations` ≙ `ShiftTrackingFootOdometryPositionsTermination` / `...OrientationsTermination` (:739-867),
+    `shift_motor_positions` ≙ `ShiftTrackingMotorPositionsTermination` (compositions/generic.py:664-716).  A row whose family or
+    cutoff is absent stays zero and its property raises.
+
+    A horizon selects its family and names its source block, of the same engine: `odometry_horizon` reads `odom_pose` of
+    `locomotion` (`LocomotionQuantities`), `foot_horizon` `relative_pose` and `reference_relative_pose` of `foot_poses`
+    (`FootPoseQuantities`, two feet or more: the foot reference stays that block's tensor), `motor_horizon` `position` of
+    `actuation` (`ActuatedJointQuantities`, joint side).  Refresh the source blocks first.  The other references are tensors of
+    this block the caller fills (they stand for what `QuantityEvalMode.REFERENCE` reads from a trajectory database):
+    `reference_odom_pose` `[3][B]` and `reference_position` `[M][B]`, zero at first; `set_reference_from_current(lane_mask)`
+    copies the current true values into every reference on the masked lanes.
+
+    The windows are state of the block: `count` `[B]`, the number of pushes of every lane since its restart, and the rings
+    `odom_ring`, `yaw_prev`, `yaw_ring`, `foot_ring`, `motor_ring` (layouts: include/jiminy_hip.h).  `reset(lane_mask)` restarts
+    the windows of the masked lanes (every lane without a mask) and keeps the other lanes bit for bit, rings and counter
+    included; `refresh()` pushes one environment step on every lane: call it once per step.  Both are one launch on the
+    engine's stream, without allocation, copy or synchronisation, and no launch argument changes from step to step.  The
+    tensors never change identity.  One window per family and block: other horizons take a second block."""
+
+    def __init__(self, engine, *, locomotion: Optional["LocomotionQuantities"] = None, foot_poses: Optional["FootPoseQuantities"] = None,
+                 actuation: Optional["ActuatedJointQuantities"] = None, odometry_horizon: Optional[float] = None,
+                 foot_horizon: Optional[float] = None, motor_horizon: Optional[float] = None,
+                 odometry_cutoff: Optional[float] = None, step_dt: float) -> None:
+        import ctypes as C
+
+        from . import _abi, tracking
+        for horizon, block, what, keyword in ((odometry_horizon, locomotion, "odometry_horizon", "locomotion"),
+                                              (foot_horizon, foot_poses, "foot_horizon", "foot_poses"),
+                                              (motor_horizon, actuation, "motor_horizon", "actuation")):
+            if horizon is not None and block is None:
+                raise ValueError(f"{what} reads the {keyword} block: give {keyword} as well")
+            if block is not None and block._eng is not engine:
+                raise ValueError(f"the {keyword} block belongs to another engine")
+        if odometry_cutoff is not None and not float(odometry_cutoff) > 0.0:
+            raise ValueError("a reward cutoff must be positive")
+        if odometry_cutoff is not None and odometry_horizon is None:
+            raise ValueError("odometry_cutoff rewards the drift of the odometry pose: give odometry_horizon as well")
+        if motor_horizon is not None and actuation.motor_side:
+            raise ValueError("the motor windows read joint-side positions: the actuation block was built with motor_side=True")
+        self.plan = tracking.build_plan(step_dt=step_dt, odometry_horizon=odometry_horizon, foot_horizon=foot_horizon,
+                                        motor_horizon=motor_horizon,
+                                        n_feet=None if foot_horizon is None else foot_poses.plan.n_feet,
+                                        n_motors=None if motor_horizon is None else actuation.plan.n_motors)
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._locomotion = locomotion if odometry_horizon is not None else None
+        self._foot_poses = foot_poses if foot_horizon is not None else None
+        self._actuation = actuation if motor_horizon is not None else None
+        self.odometry_horizon = None if odometry_horizon is None else float(odometry_horizon)
+        self.foot_horizon = None if foot_horizon is None else float(foot_horizon)
+        self.motor_horizon = None if motor_horizon is None else float(motor_horizon)
+        self.odometry_cutoff = None if odometry_cutoff is None else float(odometry_cutoff)
+        B, p = engine.batch_size, self.plan
+        new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
+        self.scalars, self.count = new(6), new(dtype=torch.int32)
+        self.reference_odom_pose = self.delta_odom = self.delta_odom_reference = None
+        self.odom_ring = self.yaw_prev = self.yaw_ring = self.foot_ring = self.reference_position = self.motor_ring = None
+        if p.max_stack_odom:
+            self.reference_odom_pose, self.delta_odom, self.delta_odom_reference = new(3), new(3), new(3)
+            self.odom_ring, self.yaw_prev, self.yaw_ring = new(p.max_stack_odom, 4), new(2), new(p.max_stack_odom - 1, 2)
+        if p.max_stack_foot:
+            self.foot_ring = new(2, p.max_stack_foot)
+        if p.max_stack_motor:
+            self.reference_position, self.motor_ring = new(p.n_motors), new(p.max_stack_motor)
+        self._io = _abi.TrackingIO()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_tracking_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep
+
+    @property
+    def fieldnames(self):
+        feet = self._foot_poses.foot_frame_names if self._foot_poses is not None else []
+        motors = self._actuation.plan.motor_names if self._actuation is not None else []
+        return tracking_fieldnames(feet, motors)
+
+    @property
+    def reference_relative_pose(self) -> torch.Tensor:
+        """The reference of the foot windows: the tensor of the foot pose quantities block."""
+        if self._foot_poses is None:
+            raise ValueError("the block has no foot windows: build it with foot_horizon")
+        return self._foot_poses.reference_relative_pose
+
+    def _scalar(self, row: int, present: bool, keyword: str) -> torch.Tensor:
+        if not present:
+            raise ValueError(f"the block does not evaluate this value: build it with {keyword}")
+        return self.scalars[row]
+
+    @property
+    def drift_odom_position(self) -> torch.Tensor:
+        return self._scalar(0, self._locomotion is not None, "odometry_horizon")
+
+    @property
+    def drift_odom_orientation(self) -> torch.Tensor:
+        return self._scalar(1, self._locomotion is not None, "odometry_horizon")
+
+    @property
+    def reward_odom_pose(self) -> torch.Tensor:
+        return self._scalar(2, self.odometry_cutoff is not None, "odometry_cutoff")
+
+    @property
+    def shift_foot_positions(self) -> torch.Tensor:
+        return self._scalar(3, self._foot_poses is not None, "foot_horizon")
+
+    @property
+    def shift_foot_orientations(self) -> torch.Tensor:
+        return self._scalar(4, self._foot_poses is not None, "foot_horizon")
+
+    @property
+    def shift_motor_positions(self) -> torch.Tensor:
+        return self._scalar(5, self._actuation is not None, "motor_horizon")
+
+    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        if lane_mask is None:
+            return None
+        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
+        if tuple(mask.shape) != (self._eng.batch_size,):
+            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
+        return mask
+
+    def _launch(self, mode: int, mask: Optional[torch.Tensor]) -> None:
+        eng, io = self._eng, self._io
+
+        def ptr(t: Optional[torch.Tensor], dtype=None):
+            if t is None:
+                return None
+            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
+                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+            return t.data_ptr()
+        io.odom_pose = ptr(self._locomotion.odom_pose) if self._locomotion is not None else None
+        io.relative_pose = ptr(self._foot_poses.relative_pose) if self._foot_poses is not None else None
+        io.reference_relative_pose = ptr(self._foot_poses.reference_relative_pose) if self._foot_poses is not None else None
+        io.position = ptr(self._actuation.position) if self._actuation is not None else None
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.count = ptr(self.count, torch.int32)
+        for name in ("reference_odom_pose", "reference_position", "odom_ring", "yaw_prev", "yaw_ring", "foot_ring", "motor_ring",
+                     "delta_odom", "delta_odom_reference", "scalars"):
+            setattr(io, name, ptr(getattr(self, name)))
+        self._check(self._L.jm_block_tracking(self._plan, self._dtype, eng.batch_size, self._C.byref(io), mode,
+                                              self.odometry_cutoff or 0.0, eng._stream()))
+
+    def set_reference_from_current(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The current true values become the references of the masked lanes (every lane without a mask): the odometry pose,
+        the motor positions and, through `FootPoseQuantities.set_reference_from_current`, the relative foot poses.  The windows
+        follow at the next `refresh` / `reset`."""
+        mask = self._mask(lane_mask)
+        pairs = []
+        if self._locomotion is not None:
+            pairs.append((self._locomotion.odom_pose, self.reference_odom_pose))
+        if self._actuation is not None:
+            pairs.append((self._actuation.position, self.reference_position))
+        for src, dst in pairs:
+            if mask is None:
+                dst.copy_(src)
+            else:
+                torch.where(mask.bool(), src, dst, out=dst)
+        if self._foot_poses is not None:
+            self._foot_poses.set_reference_from_current(lane_mask)
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """Restart the windows of the masked lanes (every lane without a mask) at the values of their new episode; the other
+        lanes keep every tensor, the rings and the counter bit for bit.  Call it after the reset of the source blocks."""
+        from . import tracking
+        self._launch(tracking.RESTART, self._mask(lane_mask))
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream, behind the refresh of the source blocks: one environment step pushed into the
+        windows of every lane."""
+        from . import tracking
+        self._launch(tracking.PUSH, None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_tracking_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

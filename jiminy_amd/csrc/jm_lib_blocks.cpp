@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities and of the foot pose quantities, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities and of the tracking windows, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include "jm_locomotion.h"
 #include "jm_actuation.h"
 #include "jm_footposes.h"
+#include "jm_tracking.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -106,6 +107,11 @@ struct jm_actuation_plan
 };
 // the foot pose quantities (jm_footposes.h)
 struct jm_footposes_plan
+{
+    DevicePlan dev;
+};
+// the tracking windows (jm_tracking.h)
+struct jm_tracking_plan
 {
     DevicePlan dev;
 };
@@ -416,6 +422,35 @@ int32_t jm_block_foot_poses(const jm_footposes_plan * p, int32_t dtype, int64_t 
         const jm::FootIO<T> a{(const T *)io->pose, (const T *)io->reference_relative_pose, io->lane_mask, (T *)io->mean_pose,
                               (T *)io->mean_odom_pose, (T *)io->relative_pose, (T *)io->tracking_error, (T *)io->scalars};
         hipLaunchKernelGGL((jm::k_foot_poses<T>), grid, dim3(256), 0, s, it, dt, a, position_cutoff, orientation_cutoff, (long long)B);
+    });
+}
+
+int32_t jm_tracking_plan_create(const jm_tracking_desc * desc, jm_tracking_plan ** out)
+{
+    return plan_create("jm_tracking_plan_create", desc, out, jm::tracking_pack);
+}
+
+int32_t jm_tracking_plan_destroy(jm_tracking_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_tracking(const jm_tracking_plan * p, int32_t dtype, int64_t B, const jm_tracking_io * io, int32_t mode,
+                          double odometry_cutoff, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_tracking: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_tracking: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_tracking: bad dtype");
+    if (mode != jm::TRK_RESTART && mode != jm::TRK_PUSH) return fail(JM_EINVAL, "jm_block_tracking: mode must be 0 (restart) or 1 (push)");
+    const int32_t * it = p->dev.it;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::TrkIO<T> a{(const T *)io->odom_pose, (const T *)io->reference_odom_pose, (const T *)io->relative_pose,
+                             (const T *)io->reference_relative_pose, (const T *)io->position, (const T *)io->reference_position,
+                             io->lane_mask, io->count, (T *)io->odom_ring, (T *)io->yaw_prev, (T *)io->yaw_ring, (T *)io->foot_ring,
+                             (T *)io->motor_ring, (T *)io->delta_odom, (T *)io->delta_odom_reference, (T *)io->scalars};
+        hipLaunchKernelGGL((jm::k_tracking<T>), grid, dim3(256), 0, s, it, a, (int)mode, odometry_cutoff, (long long)B);
     });
 }
 

@@ -388,6 +388,8 @@ JM_DEV double rsqrt_(double x)
 JM_DEV float rsqrt_(float x) { return 1.0f / ::sqrtf(x); }
 JM_DEV double trunc_(double x) { return ::trunc(x); }
 JM_DEV float trunc_(float x) { return ::truncf(x); }
+JM_DEV double floor_(double x) { return ::floor(x); }
+JM_DEV float floor_(float x) { return ::floorf(x); }
 // tanh(x) = e / (e + 2), e = expm1(2 |x|) = 2^n (expm1(r) + 1) - 1 with 2|x| = n ln2 + r, |r| <= ln2 / 2 (degree-13
 // Taylor polynomial of expm1, truncation 4e-18 relative); |x| >= 20 saturates.  < 3 ulp (2.8 near x = 0.22: the
 // roundings of e, e + 2 and the quotient add up); replaces ocml's

@@ -430,7 +430,8 @@ class WalkerVecEnv(VecJiminyEnv):
     def __init__(self, *args: Any, reward_mixture: Optional[Dict[str, float]] = None,
                  frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
                  locomotion_quantities: Optional[Dict[str, Any]] = None, actuated_joints: Optional[Dict[str, Any]] = None,
-                 foot_poses: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
+                 foot_poses: Optional[Dict[str, Any]] = None, trajectory_tracking: Optional[Dict[str, Any]] = None,
+                 **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -461,9 +462,26 @@ class WalkerVecEnv(VecJiminyEnv):
         #   reward_mixture['foot_positions'] / ['foot_orientations']  ≙ `TrackingFootPositionsReward` /
         #                                              `TrackingFootOrientationsReward` (compositions/locomotion.py:146-214), weights
         #                                              on the reward rows of the block's `position_cutoff` / `orientation_cutoff`
-        self.frames = self.locomotion = self.actuation = self.foot_poses = None
+        # optional `blocks.TrackingWindows` (its constructor's keywords but the source blocks, which are the environment's own,
+        # and `step_dt`, the environment's), reset and refreshed behind the other four blocks and exposed as `tracking`.  Just
+        # before each of its launches the environment calls `_update_tracking_reference(lane_mask)`, where a subclass writes
+        # the reference tensors; what reads the block:
+        #   drift_odom_position / drift_odom_orientation=(threshold, grace_period)
+        #                                              ≙ `DriftTrackingBaseOdometryPositionTermination` / `...OrientationTermination`
+        #                                              (compositions/locomotion.py:623-736)
+        #   shift_foot_positions / shift_foot_orientations / shift_motor_positions=(threshold, grace_period)
+        #                                              ≙ `ShiftTrackingFootOdometryPositionsTermination` / `...OrientationsTermination`
+        #                                              (:739-867), `ShiftTrackingMotorPositionsTermination` (compositions/generic.py:
+        #                                              664-716); their grace period is max(grace_period, horizon) (:451)
+        #   reward_mixture['odom_pose']                ≙ `DriftTrackingBaseOdometryPoseReward` (compositions/locomotion.py:85-120),
+        #                                              weight on the reward row of the block's `odometry_cutoff`
+        self.frames = self.locomotion = self.actuation = self.foot_poses = self.tracking = None
         self._terminations = dict(terminations or {})
-        known = ("base_roll_pitch", "min_base_height", "flying", "impact_force", "mechanical_safety", "power_consumption")
+        tracking_terms = {"drift_odom_position": "odometry_horizon", "drift_odom_orientation": "odometry_horizon",
+                          "shift_foot_positions": "foot_horizon", "shift_foot_orientations": "foot_horizon",
+                          "shift_motor_positions": "motor_horizon"}
+        known = ("base_roll_pitch", "min_base_height", "flying", "impact_force", "mechanical_safety", "power_consumption",
+                 *tracking_terms)
         unknown = set(self._terminations) - set(known)
         if unknown:
             raise ValueError(f"unknown terminations {sorted(unknown)} ({', '.join(known)})")
@@ -502,10 +520,31 @@ class WalkerVecEnv(VecJiminyEnv):
         elif {"foot_positions", "foot_orientations"} & set(self.reward_mixture):
             raise ValueError("the foot_positions and foot_orientations reward terms read the foot pose quantities block: give "
                              "foot_poses as well")
-        if set(self._terminations) - {"mechanical_safety", "power_consumption"} and frame_kinematics is None:
+        if set(tracking_terms) & set(self._terminations) and trajectory_tracking is None:
+            raise ValueError("the drift_odom_* and shift_* terminations read the tracking windows block: give "
+                             "trajectory_tracking as well")
+        if trajectory_tracking is not None:
+            trajectory_tracking = dict(trajectory_tracking)
+            for source in ("locomotion", "foot_poses", "actuation", "step_dt"):
+                if source in trajectory_tracking:
+                    raise ValueError(f"trajectory_tracking takes no '{source}': the source blocks and the step are the environment's")
+            for term, horizon in tracking_terms.items():
+                if term in self._terminations and trajectory_tracking.get(horizon) is None:
+                    raise ValueError(f"the {term} termination needs trajectory_tracking['{horizon}']")
+            if "odom_pose" in self.reward_mixture and trajectory_tracking.get("odometry_cutoff") is None:
+                raise ValueError("reward_mixture['odom_pose'] needs trajectory_tracking['odometry_cutoff']")
+            for horizon, given, keyword in (("odometry_horizon", locomotion_quantities, "locomotion_quantities"),
+                                            ("foot_horizon", foot_poses, "foot_poses"),
+                                            ("motor_horizon", actuated_joints, "actuated_joints")):
+                if trajectory_tracking.get(horizon) is not None and given is None:
+                    raise ValueError(f"trajectory_tracking['{horizon}'] reads the block of {keyword}: give {keyword} as well")
+        elif "odom_pose" in self.reward_mixture:
+            raise ValueError("the odom_pose reward term reads the tracking windows block: give trajectory_tracking as well")
+        no_frames = {"mechanical_safety", "power_consumption", *tracking_terms}
+        if set(self._terminations) - no_frames and frame_kinematics is None:
             raise ValueError("the terminations read the frame kinematics block: give frame_kinematics as well")
         if frame_kinematics is not None:
-            reading = {k: v for k, v in self._terminations.items() if k not in ("mechanical_safety", "power_consumption")}
+            reading = {k: v for k, v in self._terminations.items() if k not in no_frames}
             if foot_poses is None:
                 names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities)
             else:
@@ -516,7 +555,7 @@ class WalkerVecEnv(VecJiminyEnv):
             if locomotion_quantities is not None:
                 self.engine.enable_output("centroidal")
                 self.locomotion = blocks.LocomotionQuantities(self.engine, self.frames, **locomotion_quantities)
-            if set(self._terminations) - {"mechanical_safety", "power_consumption"}:
+            if set(self._terminations) - no_frames:
                 self._frame_root = self.frames.index("root_joint")
                 self._frame_contacts = torch.tensor([self.frames.index(n) for n in self.model.contacts], dtype=torch.long, device=self.device)
                 if "base_roll_pitch" in self._terminations:
@@ -528,6 +567,9 @@ class WalkerVecEnv(VecJiminyEnv):
                     raise ValueError("min_base_height needs a model with contact frames")
         if actuated_joints is not None:
             self.actuation = blocks.ActuatedJointQuantities(self.engine, step_dt=self.step_dt, **actuated_joints)
+        if trajectory_tracking is not None:
+            self.tracking = blocks.TrackingWindows(self.engine, locomotion=self.locomotion, foot_poses=self.foot_poses,
+                                                   actuation=self.actuation, step_dt=self.step_dt, **trajectory_tracking)
         m = self.model
         lim = torch.tensor([mo.effort_limit * mo.velocity_limit for mo in m.motors], dtype=self.dtype)
         self._power_consumption_max = float(lim.sum())  # locomotion.py:230-236
@@ -584,6 +626,12 @@ class WalkerVecEnv(VecJiminyEnv):
             self._dir_sum.copy_(torch.where(lane_mask, y0, self._dir_sum))
             self._dir_n.copy_(torch.where(lane_mask, torch.ones_like(self._dir_n), self._dir_n))
 
+    def _update_tracking_reference(self, lane_mask: Optional[torch.Tensor]) -> None:
+        """Called just before every launch of the tracking windows block: with the mask of `reset_lanes` before a restart of
+        those lanes, with None before the restart of every lane (`reset`) and before the push of a step.  The place where a
+        subclass writes the reference tensors of `tracking` (and of `foot_poses`), for instance gathered from a trajectory
+        by the step count of every lane.  Nothing by default: the references stay what the caller wrote."""
+
     def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
         out = super().reset(seed, options)
         self._direction_restart(None)
@@ -595,6 +643,9 @@ class WalkerVecEnv(VecJiminyEnv):
             self.foot_poses.reset(None)
         if self.actuation is not None:
             self.actuation.reset(None)
+        if self.tracking is not None:
+            self._update_tracking_reference(None)
+            self.tracking.reset(None)
         return out
 
     def reset_lanes(self, lane_mask: torch.Tensor) -> None:
@@ -608,6 +659,9 @@ class WalkerVecEnv(VecJiminyEnv):
             self.foot_poses.reset(lane_mask)
         if self.actuation is not None:
             self.actuation.reset(lane_mask)
+        if self.tracking is not None:
+            self._update_tracking_reference(lane_mask)
+            self.tracking.reset(lane_mask)
 
     def _after_step(self):
         self._dir_sum += self.engine.robot_state.q[1].to(torch.float64)
@@ -622,6 +676,9 @@ class WalkerVecEnv(VecJiminyEnv):
             self.foot_poses.refresh()
         if self.actuation is not None:
             self.actuation.refresh()
+        if self.tracking is not None:
+            self._update_tracking_reference(None)
+            self.tracking.refresh()
         return super()._after_step()
 
     def base_relative_height(self) -> torch.Tensor:
@@ -659,6 +716,16 @@ class WalkerVecEnv(VecJiminyEnv):
                 act = self.actuation
                 value = act.power_average if act.plan.has_horizon else act.power      # (compositions/generic.py:640-650)
                 terminated = terminated | ((t >= grace) & (value > max_power))
+            for term in ("drift_odom_position", "drift_odom_orientation"):
+                if term in self._terminations:
+                    threshold, grace = self._terminations[term]
+                    terminated = terminated | ((t >= grace) & (getattr(self.tracking, term) > threshold))
+            for term, horizon in (("shift_foot_positions", "foot_horizon"), ("shift_foot_orientations", "foot_horizon"),
+                                  ("shift_motor_positions", "motor_horizon")):
+                if term in self._terminations:
+                    threshold, grace = self._terminations[term]
+                    grace = max(grace, getattr(self.tracking, horizon))       # (compositions/generic.py:451)
+                    terminated = terminated | ((t >= grace) & (getattr(self.tracking, term) > threshold))
         return terminated, truncated
 
     def compute_reward(self, terminated: torch.Tensor) -> torch.Tensor:
@@ -687,6 +754,8 @@ class WalkerVecEnv(VecJiminyEnv):
             total += self.reward_mixture["foot_positions"] * self.foot_poses.reward_foot_positions
         if "foot_orientations" in self.reward_mixture:
             total += self.reward_mixture["foot_orientations"] * self.foot_poses.reward_foot_orientations
+        if "odom_pose" in self.reward_mixture:
+            total += self.reward_mixture["odom_pose"] * self.tracking.reward_odom_pose
         return total
 
 
@@ -910,6 +979,9 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
                                           "of the captured step")
             if whole_step and self.actuation is not None:
                 raise NotImplementedError("whole-step graphs do not take the actuated-joint quantities block: the restart of "
+                                          "its windows at reset is not part of the captured step")
+            if whole_step and self.tracking is not None:
+                raise NotImplementedError("whole-step graphs do not take the tracking windows block: the restart of "
                                           "its windows at reset is not part of the captured step")
             if whole_step and self._mahony is not None:
                 raise NotImplementedError("whole-step graphs do not take the MahonyFilter / BodyObserver blocks: their "
