@@ -973,6 +973,75 @@ int32_t jm_tracking_plan_destroy(jm_tracking_plan * plan);
 int32_t jm_block_tracking(const jm_tracking_plan * plan, int32_t dtype, int64_t batch_size, const jm_tracking_io * io, int32_t mode,
                           double odometry_cutoff, void * stream);
 
+/* ---- Reference trajectories: a device-resident dataset of recorded trajectories and the state of each lane's selected
+ * trajectory at the lane's own time -- what `QuantityEvalMode.REFERENCE` reads; batched, one lane = one environment, one
+ * launch per query.  New symbols only: no existing structure or signature changed with them.  Reference:
+ * python/jiminy_py/src/jiminy_py/dynamics.py:296-388 (`Trajectory.get`: the time mode, `bisect_left`, the choice of a sample
+ * or `alpha`, `pin.interpolate` of `q`, the linear interpolation of the other fields, the odometry of a wrapping time),
+ * :207-213 (the stride), :31 (`TRAJ_INTERP_TOL`); python/gym_jiminy/common/gym_jiminy/common/bases/quantities.py:870-1210
+ * (`DatasetTrajectoryQuantity`: the registry, the selection and the time offset, `lock`); utils/math.py:725-954 (`log3`, `exp3`,
+ * `log6`, `exp6`); quantities/locomotion.py:158-220 (`BaseOdometryPose`), restated operation for operation.
+ * jm_trajectory_desc: the dataset and the layout of `q`.  `n_trajectories` trajectories concatenated along the sample axis:
+ *   `sample_start[n_trajectories + 1]` (from 0 to `n_samples`, at least 2 samples each), `times[n_samples]` (float64, finite,
+ *   not decreasing inside a trajectory; two equal consecutive times are t-, t+), `mode[n_trajectories]` (0 raise, 1 wrap,
+ *   2 clip), `stride[n_trajectories][6]` (float64, `log6(M_end * M_start^-1)` of the free-flyer, linear then angular; read
+ *   only with a free-flyer, NULL without one), `data[n_samples][R]` (HOST memory, scalar type `dtype`, sample-major; a row is
+ *   q (nq), then v (nv) with `fields` bit 0, a (nv) with bit 1, command (n_command) with bit 2).  The joint table: per joint its
+ *   kind (1-4 revolute, 5 unbounded revolute: cos, sin; 6 spherical: quaternion xyzw; 7 free-flyer: position, quaternion; 8-11
+ *   prismatic -- the kinds of jm_frames_desc) and its first row of `q`; a free-flyer is joint 0 at row 0.  `motor_q_index
+ *   [n_motors]`: the `q` rows of the motors, each the row of a one-row joint.  jm_trajectory_plan_create validates all of it
+ *   (JM_EINVAL + jm_last_error naming the entry, before any device call) and copies the tables and the samples to the device;
+ *   the plan is immutable afterwards.
+ * jm_trajectory_io: the device pointers of one launch.  Inputs: `time` (float64 `[B]`, the lane's episode time), `trajectory`
+ *   (int32 `[B]`), `time_offset` (float64 `[B]`), `lane_mask` (uint8 `[B]`, NULL: every lane; other lanes are not touched).
+ *   Outputs `[rows][B]` of the scalar type, each may be NULL: `q [nq]`, `v`, `a` `[nv]`, `command [n_command]` (absent fields
+ *   are never written), `odom_pose [3]` (x, y, yaw of the free-flyer, the expression of jm_block_locomotion; free-flyer only),
+ *   `position [n_motors]` (`q[motor_q_index]`), `status` (int32 `[3][B]`: flags, `n_steps`, the right sample's index inside the
+ *   trajectory).  Flags: bit 0 the query time is out of range in mode raise (the reference raises; the launch goes on with
+ *   the clipped time), or is not finite; bit 1 `trajectory` is outside the dataset (nothing else is written for the lane).
+ * jm_block_trajectory_state: the query time `time + time_offset`, the mode handling, the search and `alpha` are float64
+ *   for both dtypes.  `dtype` must be the plan's.  No argument changes from step to step, so the launch can be part of a
+ *   captured graph. */
+typedef struct jm_trajectory_desc
+{
+    int32_t dtype;
+    int32_t n_trajectories;
+    int32_t n_samples;
+    const int32_t * sample_start;
+    const double * times;
+    const int32_t * mode;
+    const double * stride;
+    int32_t nq;
+    int32_t nv;
+    int32_t n_command;
+    int32_t fields;
+    const void * data;
+    int32_t n_joints;
+    const int32_t * joint_kind;
+    const int32_t * joint_q_index;
+    int32_t n_motors;
+    const int32_t * motor_q_index;
+} jm_trajectory_desc;
+typedef struct jm_trajectory_io
+{
+    const double * time;
+    const int32_t * trajectory;
+    const double * time_offset;
+    const uint8_t * lane_mask;
+    void * q;
+    void * v;
+    void * a;
+    void * command;
+    void * odom_pose;
+    void * position;
+    int32_t * status;
+} jm_trajectory_io;
+typedef struct jm_trajectory_plan jm_trajectory_plan;
+int32_t jm_trajectory_plan_create(const jm_trajectory_desc * desc, jm_trajectory_plan ** out);
+int32_t jm_trajectory_plan_destroy(jm_trajectory_plan * plan);
+int32_t jm_block_trajectory_state(const jm_trajectory_plan * plan, int32_t dtype, int64_t batch_size, const jm_trajectory_io * io,
+                                  void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

@@ -175,6 +175,25 @@ class TrackingIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in TRACKING_IO_FIELDS]
 
 
+class TrajectoryDesc(C.Structure):
+    """jm_trajectory_desc: the dataset and the layout of `q` of the reference trajectories (jiminy_amd.trajectory builds it)."""
+    _fields_ = [
+        ("dtype", C.c_int32), ("n_trajectories", C.c_int32), ("n_samples", C.c_int32), ("sample_start", _pi), ("times", _pd),
+        ("mode", _pi), ("stride", _pd), ("nq", C.c_int32), ("nv", C.c_int32), ("n_command", C.c_int32), ("fields", C.c_int32),
+        ("data", C.c_void_p), ("n_joints", C.c_int32), ("joint_kind", _pi), ("joint_q_index", _pi), ("n_motors", C.c_int32),
+        ("motor_q_index", _pi),
+    ]
+
+
+TRAJECTORY_IO_FIELDS = ("time", "trajectory", "time_offset", "lane_mask", "q", "v", "a", "command", "odom_pose", "position",
+                        "status")
+
+
+class TrajectoryIO(C.Structure):
+    """jm_trajectory_io: the device pointers of one launch of jm_block_trajectory_state; the outputs each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in TRAJECTORY_IO_FIELDS]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

@@ -58,6 +58,7 @@ ABI_SYMBOLS = (
     "jm_actuation_plan_create", "jm_actuation_plan_destroy", "jm_block_actuation",
     "jm_footposes_plan_create", "jm_footposes_plan_destroy", "jm_block_foot_poses",
     "jm_tracking_plan_create", "jm_tracking_plan_destroy", "jm_block_tracking",
+    "jm_trajectory_plan_create", "jm_trajectory_plan_destroy", "jm_block_trajectory_state",
 )
 
 
@@ -136,6 +137,9 @@ class HipLibrary:
         L.jm_tracking_plan_create.argtypes = [C.POINTER(_abi.TrackingDesc), C.POINTER(vp)]
         L.jm_tracking_plan_destroy.argtypes = [vp]
         L.jm_block_tracking.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrackingIO), C.c_int32, C.c_double, vp]
+        L.jm_trajectory_plan_create.argtypes = [C.POINTER(_abi.TrajectoryDesc), C.POINTER(vp)]
+        L.jm_trajectory_plan_destroy.argtypes = [vp]
+        L.jm_block_trajectory_state.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrajectoryIO), vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

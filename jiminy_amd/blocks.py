@@ -47,6 +47,11 @@ rewards against a reference of those relative poses, from the `pose` of a `Frame
 against a reference motion over sliding windows of environment steps, and the reward on the drift, from the tensors of the
 three blocks above: one HIP launch per refresh (csrc/jm_tracking.h) driven by a plan that jiminy_amd/tracking.py builds;
 specification: tests/golden/ref_tracking.npz.
+
+`ReferenceTrajectory` gives the state of a recorded trajectory at every lane's own time (a device-resident dataset, a per-lane
+selection and time offset; time modes, bisection, Lie-group interpolation, wrap odometry): the reference side of the four
+blocks above.  One HIP launch per query (csrc/jm_trajectory.h) driven by a plan that jiminy_amd/trajectory.py builds;
+specification: tests/golden/ref_trajectory.npz.
 """
 from __future__ import annotations
 
@@ -405,6 +410,10 @@ class FrameKinematics:
     `BaseSpatialAverageVelocity` (quantities/locomotion.py:222-288); `pose_mean` `[7][K][B]` ≙ `AverageFrameXYZQuat`
     (:1289-1360); `quat_no_yaw` `[4][K][B]` ≙ `AverageFrameRollPitch` (:1363-1426).
 
+    `state=(q, v)`: `[rows][B]` tensors read instead of the engine's `q`, `v` (the state of a reference trajectory,
+    `ReferenceTrajectory.q` / `.v`), without the per-lane joint placements: the reference evaluates a trajectory on the
+    trajectory's own robot.
+
     `reset(lane_mask)` evaluates the frames at the state the engine's `start` / `reset_lanes` wrote and makes it the previous
     pose of the average; `refresh()` evaluates them at the engine's current `q`, `v` (with the per-lane joint placements when
     the engine has a biased model bound); `refresh_average(step_dt)` averages between the pose of the previous call (or
@@ -412,12 +421,25 @@ class FrameKinematics:
     identity."""
 
     def __init__(self, engine, frame_names, *, reference_frames=None, compute_rpy: bool = False, compute_velocity: bool = True,
-                 average: bool = False) -> None:
+                 average: bool = False, state=None) -> None:
         import ctypes as C
 
         from . import _abi, frames
         self._C = C
         self._eng = engine
+        # `state`: a pair (q, v) of `[rows][B]` tensors read instead of the engine's fields (v may be None without
+        # `compute_velocity`) -- the state of a reference trajectory, which the reference evaluates on the trajectory's own
+        # robot, not on the per-episode biased model: the lane's joint placements are not applied then
+        self._state = None
+        if state is not None:
+            q, v = state
+            if tuple(q.shape) != (engine.model.nq, engine.batch_size):
+                raise ValueError(f"state q must have shape ({engine.model.nq}, {engine.batch_size})")
+            if v is not None and tuple(v.shape) != (engine.model.nv, engine.batch_size):
+                raise ValueError(f"state v must have shape ({engine.model.nv}, {engine.batch_size})")
+            if v is None and compute_velocity:
+                raise ValueError("the frame velocity needs v: give state=(q, v) or compute_velocity=False")
+            self._state = (q, v)
         self._L = engine._lib.L
         self._check = engine._lib.check
         self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
@@ -459,10 +481,13 @@ class FrameKinematics:
 
     def _kinematics(self, mask: Optional[torch.Tensor], pose_prev: Optional[torch.Tensor]) -> None:
         eng = self._eng
-        model_lane = eng._fields.get("model_lane")
+        if self._state is not None:
+            q, v, model_lane = self._state[0], self._state[1], None
+        else:
+            q, v, model_lane = eng.field("q"), eng.field("v"), eng._fields.get("model_lane")
         self._check(self._L.jm_block_frame_kinematics(
-            self._plan, self._dtype, eng.batch_size, self._vp(eng.field("q")),
-            self._vp(eng.field("v")) if self.compute_velocity else None, self._vp(model_lane),
+            self._plan, self._dtype, eng.batch_size, self._vp(q),
+            self._vp(v) if self.compute_velocity else None, self._vp(model_lane),
             None if mask is None else self._C.c_void_p(mask.data_ptr()), self._vp(self.pose), self._vp(pose_prev),
             self._vp(self.rpy), self._vp(self.velocity), eng._stream()))
 
@@ -1136,6 +1161,173 @@ class TrackingWindows:
         if plan:
             try:
                 self._L.jm_tracking_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+def trajectory_fieldnames(model, fields: int, motor_names):
+    """Names of the rows of the tensors of a `ReferenceTrajectory` block."""
+    from .trajectory import HAS_A, HAS_COMMAND, HAS_V, STATUS
+    names = {"q": [f"ReferenceQ.{i}" for i in range(model.nq)], "odom_pose": [f"ReferenceOdom.{e}" for e in ("X", "Y", "Yaw")],
+             "position": [f"{n}.ReferencePosition" for n in motor_names], "status": list(STATUS)}
+    if fields & HAS_V:
+        names["v"] = [f"ReferenceV.{i}" for i in range(model.nv)]
+    if fields & HAS_A:
+        names["a"] = [f"ReferenceA.{i}" for i in range(model.nv)]
+    if fields & HAS_COMMAND:
+        names["command"] = [f"{m.name}.ReferenceCommand" for m in model.motors]
+    return names
+
+
+class ReferenceTrajectory:
+    """The state of a recorded trajectory at every lane's own time: what `QuantityEvalMode.REFERENCE` reads.  ≙
+    `DatasetTrajectoryQuantity` (bases/quantities.py:870-1210) over `Trajectory.get` (jiminy_py/dynamics.py:296-388).
+
+    `dataset` is `{name: (jiminy_amd.trajectory.Trajectory, mode)}`, ordered like the reference's registry, mode "raise",
+    "wrap" or "clip"; it is copied to the device once and immutable afterwards (the reference's `lock()`).  `names` lists the
+    trajectories in order.  Per lane: `trajectory` `[B]` (int32, the selected trajectory) and `time_offset` `[B]` (float64),
+    written by `select(name_or_indices, lane_mask=None, time_offset_ratio=0.0)`: `time_offset = t_start + ratio * (t_end -
+    t_start)` of the selected trajectory (:1171-1174), the ratio a number or a `[B]` tensor.
+
+    `query(time, lane_mask=None)` evaluates the selected trajectories at `time + time_offset` (`time`: float64 `[B]`, the
+    lanes' episode times) into `q` `[nq][B]`, `v`, `a` `[nv][B]`, `command` `[n_motors][B]` (the fields the dataset carries;
+    None otherwise), `odom_pose` `[3][B]` (x, y, yaw of the free-flyer, the function of `LocomotionQuantities.odom_pose`; None
+    without a free-flyer), `position` `[M][B]` (`q` at the motors' rows, joint side) and `status` `[3][B]` (int32: flags,
+    `n_steps` of a wrapping time, index of the right sample).  `out_of_range` is bit 0 of the flags: the lanes where the
+    reference raises "Query time out-of-range." (mode "raise"); they carry the state at the clipped time.  One launch on the
+    engine's stream, without allocation, copy or synchronisation; no launch argument changes from call to call and the
+    tensors never change identity.  Lanes outside `lane_mask` keep every tensor bit for bit.
+
+    `bind_references(tracking)` makes the block write `odom_pose` / `position` straight into `reference_odom_pose` /
+    `reference_position` of a `TrackingWindows` block (these then ARE this block's tensors).  `actuation` (an
+    `ActuatedJointQuantities` block) names the motors of `position`; default: the model's."""
+
+    def __init__(self, engine, dataset, *, actuation: Optional["ActuatedJointQuantities"] = None) -> None:
+        import ctypes as C
+        import os
+
+        import numpy as np
+
+        from . import _abi, trajectory
+        if os.environ.get("JIMINY_AMD_TENSOR_BLOCKS", "0") == "1":
+            raise NotImplementedError("the reference trajectories have no tensor-program form (JIMINY_AMD_TENSOR_BLOCKS=1): "
+                                      "the lookup exists as the HIP kernel only")
+        if actuation is not None and actuation._eng is not engine:
+            raise ValueError("the actuation block belongs to another engine")
+        motor_rows = None if actuation is None else [int(i) for i in actuation.plan.arrays["idx_q"]]
+        self.plan = trajectory.build_plan(engine.model, dataset, motor_rows)
+        self.names = list(self.plan.names)
+        self._motor_names = list(actuation.plan.motor_names) if actuation is not None else \
+            [m.name for m in engine.model.motors][:self.plan.n_motors]
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        B, p = engine.batch_size, self.plan
+        new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
+        self.q = new(p.nq)
+        self.v = new(p.nv) if p.fields & trajectory.HAS_V else None
+        self.a = new(p.nv) if p.fields & trajectory.HAS_A else None
+        self.command = new(p.n_command) if p.fields & trajectory.HAS_COMMAND else None
+        self.odom_pose = new(3) if p.has_freeflyer else None
+        self.position = new(p.n_motors) if p.n_motors else None
+        self.status = new(3, dtype=torch.int32)
+        self.trajectory = new(dtype=torch.int32)
+        self.time_offset = new(dtype=torch.float64)
+        self._interval = torch.as_tensor(p.time_interval, dtype=torch.float64, device=engine.device)
+        self.time_offset.fill_(float(p.time_interval[0, 0]))
+        self._io = _abi.TrajectoryIO()
+        desc, keep = self.plan.desc(np.float64 if engine.dtype == torch.float64 else np.float32)
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_trajectory_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep
+
+    @property
+    def fieldnames(self):
+        return trajectory_fieldnames(self._eng.model, self.plan.fields, self._motor_names)
+
+    @property
+    def out_of_range(self) -> torch.Tensor:
+        """`[B]` bool: the query time of the lane was out of range in mode "raise" at the last `query`."""
+        return (self.status[0] & 1).bool()
+
+    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        if lane_mask is None:
+            return None
+        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
+        if tuple(mask.shape) != (self._eng.batch_size,):
+            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
+        return mask
+
+    def select(self, name_or_indices, lane_mask: Optional[torch.Tensor] = None, time_offset_ratio=0.0) -> None:
+        """Select a trajectory by name (every masked lane the same) or by a `[B]` tensor of indices, and set the time offset
+        of the masked lanes (every lane without a mask) from `time_offset_ratio`, a number or a `[B]` tensor."""
+        eng, B = self._eng, self._eng.batch_size
+        if isinstance(name_or_indices, str):
+            if name_or_indices not in self.names:
+                raise KeyError(f"no trajectory named '{name_or_indices}' (registered: {', '.join(self.names)})")
+            index = torch.full((B,), self.names.index(name_or_indices), dtype=torch.int64, device=eng.device)
+        else:
+            index = torch.as_tensor(name_or_indices, device=eng.device).to(torch.int64)
+            if index.ndim == 0:
+                index = index.expand(B)
+            if tuple(index.shape) != (B,):
+                raise ValueError(f"the trajectory indices must have shape ({B},)")
+        mask = None if lane_mask is None else self._mask(lane_mask).bool()
+        chosen = index if mask is None else index[mask]
+        if chosen.numel() and (int(chosen.min()) < 0 or int(chosen.max()) >= len(self.names)):
+            raise IndexError(f"trajectory index out of range [0, {len(self.names)})")
+        ratio = torch.as_tensor(time_offset_ratio, dtype=torch.float64, device=eng.device)
+        if ratio.ndim == 0:
+            ratio = ratio.expand(B)
+        if tuple(ratio.shape) != (B,):
+            raise ValueError(f"time_offset_ratio must be a number or have shape ({B},)")
+        interval = self._interval[index.clamp(0, len(self.names) - 1)]
+        offset = interval[:, 0] + ratio * (interval[:, 1] - interval[:, 0])
+        if mask is None:
+            self.trajectory.copy_(index)
+            self.time_offset.copy_(offset)
+        else:
+            torch.where(mask, index.to(torch.int32), self.trajectory, out=self.trajectory)
+            torch.where(mask, offset, self.time_offset, out=self.time_offset)
+
+    def bind_references(self, tracking: "TrackingWindows") -> None:
+        """Write `odom_pose` / `position` straight into the references of a `TrackingWindows` block of the same engine."""
+        if tracking._eng is not self._eng:
+            raise ValueError("the tracking block belongs to another engine")
+        if tracking.reference_odom_pose is not None:
+            if self.odom_pose is None:
+                raise ValueError("the odometry windows need the reference of a free-flyer: the model has none")
+            self.odom_pose = tracking.reference_odom_pose
+        if tracking.reference_position is not None:
+            if self.position is None or tuple(self.position.shape) != tuple(tracking.reference_position.shape):
+                raise ValueError("the motor windows and the trajectory block do not describe the same motors")
+            self.position = tracking.reference_position
+
+    def query(self, time: torch.Tensor, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """One launch on the engine's stream: the state of every (masked) lane's trajectory at `time + time_offset`."""
+        eng, io = self._eng, self._io
+        if time.dtype != torch.float64 or tuple(time.shape) != (eng.batch_size,) or time.device != eng.device or \
+                not time.is_contiguous():
+            raise ValueError(f"time must be a contiguous float64 tensor of shape ({eng.batch_size},) on the engine's device")
+        mask = self._mask(lane_mask)
+        io.time, io.trajectory, io.time_offset = time.data_ptr(), self.trajectory.data_ptr(), self.time_offset.data_ptr()
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        for name in ("q", "v", "a", "command", "odom_pose", "position"):
+            t = getattr(self, name)
+            if t is not None:
+                _check_block_tensor(eng, t)
+            setattr(io, name, None if t is None else t.data_ptr())
+        io.status = self.status.data_ptr()
+        self._check(self._L.jm_block_trajectory_state(self._plan, self._dtype, eng.batch_size, self._C.byref(io), eng._stream()))
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_trajectory_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities and of the tracking windows, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows and of the reference trajectories, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "jm_actuation.h"
 #include "jm_footposes.h"
 #include "jm_tracking.h"
+#include "jm_trajectory.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -114,6 +115,17 @@ struct jm_footposes_plan
 struct jm_tracking_plan
 {
     DevicePlan dev;
+};
+// the reference trajectories (jm_trajectory.h): the tables and the samples `[S][R]` in the plan's dtype
+struct jm_trajectory_plan
+{
+    DevicePlan dev;
+    void * data = nullptr;
+    int32_t dtype = 0;
+    ~jm_trajectory_plan()
+    {
+        if (data) (void)hipFree(data);
+    }
 };
 
 extern "C"
@@ -451,6 +463,48 @@ int32_t jm_block_tracking(const jm_tracking_plan * p, int32_t dtype, int64_t B, 
                              io->lane_mask, io->count, (T *)io->odom_ring, (T *)io->yaw_prev, (T *)io->yaw_ring, (T *)io->foot_ring,
                              (T *)io->motor_ring, (T *)io->delta_odom, (T *)io->delta_odom_reference, (T *)io->scalars};
         hipLaunchKernelGGL((jm::k_tracking<T>), grid, dim3(256), 0, s, it, a, (int)mode, odometry_cutoff, (long long)B);
+    });
+}
+
+int32_t jm_trajectory_plan_create(const jm_trajectory_desc * desc, jm_trajectory_plan ** out)
+{
+    const int32_t rc = plan_create("jm_trajectory_plan_create", desc, out, jm::trajectory_pack);
+    if (rc != JM_OK) return rc;
+    jm_trajectory_plan * p = *out;
+    p->dtype = desc->dtype;
+    const size_t bytes = (size_t)desc->n_samples * (size_t)jm::trajectory_row_size(desc->nq, desc->nv, desc->n_command, desc->fields) *
+                         (desc->dtype == JM_F64 ? sizeof(double) : sizeof(float));
+    hipError_t e = hipMalloc(&p->data, bytes);
+    if (e == hipSuccess) e = hipMemcpy(p->data, desc->data, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        delete p;
+        *out = nullptr;
+        return fail(JM_ERUNTIME, std::string("jm_trajectory_plan_create: ") + hipGetErrorString(e));
+    }
+    return JM_OK;
+}
+
+int32_t jm_trajectory_plan_destroy(jm_trajectory_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_trajectory_state(const jm_trajectory_plan * p, int32_t dtype, int64_t B, const jm_trajectory_io * io, void * stream)
+{
+    if (!p || !io || !io->time || !io->trajectory || !io->time_offset) return fail(JM_EINVAL, "jm_block_trajectory_state: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_trajectory_state: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_trajectory_state: bad dtype");
+    if (dtype != p->dtype) return fail(JM_EINVAL, "jm_block_trajectory_state: dtype is not the one the plan was created with");
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    const void * data = p->data;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::TrajIO<T> a{io->time, io->trajectory, io->time_offset, io->lane_mask, (T *)io->q, (T *)io->v, (T *)io->a,
+                              (T *)io->command, (T *)io->odom_pose, (T *)io->position, io->status};
+        hipLaunchKernelGGL((jm::k_trajectory_state<T>), grid, dim3(256), 0, s, it, dt, (const T *)data, a, (long long)B);
     });
 }
 

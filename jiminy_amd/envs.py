@@ -431,7 +431,7 @@ class WalkerVecEnv(VecJiminyEnv):
                  frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
                  locomotion_quantities: Optional[Dict[str, Any]] = None, actuated_joints: Optional[Dict[str, Any]] = None,
                  foot_poses: Optional[Dict[str, Any]] = None, trajectory_tracking: Optional[Dict[str, Any]] = None,
-                 **kw: Any) -> None:
+                 trajectory_database: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -475,7 +475,17 @@ class WalkerVecEnv(VecJiminyEnv):
         #                                              664-716); their grace period is max(grace_period, horizon) (:451)
         #   reward_mixture['odom_pose']                ≙ `DriftTrackingBaseOdometryPoseReward` (compositions/locomotion.py:85-120),
         #                                              weight on the reward row of the block's `odometry_cutoff`
+        # optional `blocks.ReferenceTrajectory`: `trajectory_database={"dataset": {name: (Trajectory, mode)}, "name": ...,
+        # "time_offset_ratio": 0.0}` (≙ `DatasetTrajectoryQuantity`, bases/quantities.py:870-1210; "name": the trajectory every lane
+        # starts on, default the first), exposed as `trajectory`.  It is queried at the lanes' episode times at `reset`,
+        # `reset_lanes` and after every step, before the foot pose quantities and the tracking windows, and is the source of
+        # their references: `tracking.reference_odom_pose` / `reference_position` are written by the query itself, and with
+        # `foot_poses` a second frame kinematics block over the foot frames and a second foot pose quantities block evaluate the
+        # trajectory's state (on the nominal model) into `foot_poses.reference_relative_pose`.  A lane whose query time leaves a
+        # trajectory of mode "raise" is truncated.  `_update_tracking_reference` is still called where it was: a subclass can
+        # overwrite what the database wrote.
         self.frames = self.locomotion = self.actuation = self.foot_poses = self.tracking = None
+        self.trajectory = self._reference_frames = self._reference_foot_poses = None
         self._terminations = dict(terminations or {})
         tracking_terms = {"drift_odom_position": "odometry_horizon", "drift_odom_orientation": "odometry_horizon",
                           "shift_foot_positions": "foot_horizon", "shift_foot_orientations": "foot_horizon",
@@ -570,6 +580,26 @@ class WalkerVecEnv(VecJiminyEnv):
         if trajectory_tracking is not None:
             self.tracking = blocks.TrackingWindows(self.engine, locomotion=self.locomotion, foot_poses=self.foot_poses,
                                                    actuation=self.actuation, step_dt=self.step_dt, **trajectory_tracking)
+        if trajectory_database is not None:
+            cfg = dict(trajectory_database)
+            if "dataset" not in cfg:
+                raise ValueError("trajectory_database needs 'dataset': {name: (Trajectory, mode)}")
+            dataset, name, ratio = cfg.pop("dataset"), cfg.pop("name", None), cfg.pop("time_offset_ratio", 0.0)
+            if cfg:
+                raise ValueError(f"unknown keys in trajectory_database: {sorted(cfg)} (dataset, name, time_offset_ratio)")
+            self.trajectory = blocks.ReferenceTrajectory(self.engine, dataset, actuation=self.actuation)
+            self.trajectory.select(self.trajectory.names[0] if name is None else name, None, ratio)
+            if self.tracking is not None:
+                self.trajectory.bind_references(self.tracking)
+            self._trajectory_time = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
+            self._trajectory_time_own = None if self.dtype == torch.float64 else torch.zeros_like(self._t0)
+            if self.foot_poses is not None:
+                feet = list(self.foot_poses.foot_frame_names)
+                self._reference_frames = blocks.FrameKinematics(self.engine, feet, compute_velocity=False,
+                                                                state=(self.trajectory.q, self.trajectory.v))
+                self._reference_foot_poses = blocks.FootPoseQuantities(self.engine, self._reference_frames, foot_frame_names=feet)
+                # (its relative poses ARE the reference of the true side: no copy)
+                self._reference_foot_poses.relative_pose = self.foot_poses.reference_relative_pose
         m = self.model
         lim = torch.tensor([mo.effort_limit * mo.velocity_limit for mo in m.motors], dtype=self.dtype)
         self._power_consumption_max = float(lim.sum())  # locomotion.py:230-236
@@ -632,6 +662,28 @@ class WalkerVecEnv(VecJiminyEnv):
         subclass writes the reference tensors of `tracking` (and of `foot_poses`), for instance gathered from a trajectory
         by the step count of every lane.  Nothing by default: the references stay what the caller wrote."""
 
+    def select_trajectory(self, name_or_indices, lane_mask: Optional[torch.Tensor] = None, time_offset_ratio=0.0) -> None:
+        """≙ `DatasetTrajectoryQuantity.select`: forwards to `trajectory.select`; the next query reads the selection."""
+        if self.trajectory is None:
+            raise RuntimeError("select_trajectory needs trajectory_database")
+        self.trajectory.select(name_or_indices, lane_mask, time_offset_ratio)
+
+    def _query_trajectory(self, lane_mask: Optional[torch.Tensor]) -> None:
+        """The reference state of the (masked) lanes at their episode time, and what the reference-side blocks make of it."""
+        if self._trajectory_time_own is None:
+            torch.sub(self._clock, self._t0, out=self._trajectory_time)
+        else:
+            torch.sub(self._clock, self._t0, out=self._trajectory_time_own)
+            self._trajectory_time.copy_(self._trajectory_time_own)
+        self.trajectory.query(self._trajectory_time, lane_mask)
+        if self._reference_frames is not None:
+            if lane_mask is None:
+                self._reference_frames.refresh()
+                self._reference_foot_poses.refresh()
+            else:
+                self._reference_frames.reset(lane_mask)
+                self._reference_foot_poses.reset(lane_mask)
+
     def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
         out = super().reset(seed, options)
         self._direction_restart(None)
@@ -639,6 +691,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(None)
         if self.locomotion is not None:
             self.locomotion.reset(None)
+        if self.trajectory is not None:
+            self._query_trajectory(None)
         if self.foot_poses is not None:
             self.foot_poses.reset(None)
         if self.actuation is not None:
@@ -655,6 +709,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(lane_mask)
         if self.locomotion is not None:
             self.locomotion.reset(lane_mask)
+        if self.trajectory is not None:
+            self._query_trajectory(lane_mask)
         if self.foot_poses is not None:
             self.foot_poses.reset(lane_mask)
         if self.actuation is not None:
@@ -672,6 +728,8 @@ class WalkerVecEnv(VecJiminyEnv):
                 self.frames.refresh_average(self.step_dt)
         if self.locomotion is not None:
             self.locomotion.refresh()
+        if self.trajectory is not None:
+            self._query_trajectory(None)
         if self.foot_poses is not None:
             self.foot_poses.refresh()
         if self.actuation is not None:
@@ -693,6 +751,8 @@ class WalkerVecEnv(VecJiminyEnv):
         terminated, truncated = super().has_terminated()
         z = self.engine.robot_state.q[2]
         terminated = terminated | (z < 0.5 * self._height_neutral)  # locomotion.py:381-383
+        if self.trajectory is not None:
+            truncated = truncated | self.trajectory.out_of_range        # (the reference raises "Query time out-of-range.")
         if self._terminations:
             t = self._lane_time()
             if "base_roll_pitch" in self._terminations:
@@ -983,6 +1043,9 @@ class PDControlledWalkerVecEnv(WalkerVecEnv):
             if whole_step and self.tracking is not None:
                 raise NotImplementedError("whole-step graphs do not take the tracking windows block: the restart of "
                                           "its windows at reset is not part of the captured step")
+            if whole_step and self.trajectory is not None:
+                raise NotImplementedError("whole-step graphs do not take the reference trajectories block: its query at "
+                                          "reset is not part of the captured step")
             if whole_step and self._mahony is not None:
                 raise NotImplementedError("whole-step graphs do not take the MahonyFilter / BodyObserver blocks: their "
                                           "initialisation at reset is not part of the captured step")
