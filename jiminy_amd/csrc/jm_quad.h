@@ -33,6 +33,23 @@
 #pragma once
 #include "jm_kernels.h"
 
+// JM_OUTPUT_PASS_BEGIN: start of the output pass of the step kernels -- a compiler-only memory barrier (JM_REFRESH) that
+// also leaves a comment in the assembly, so that the pass can be found there (from that line to the end of the program:
+// tools/output_pass_check.py).
+// JM_WAIT_VMEM: wait for the vector-memory operations in flight (s_waitcnt vmcnt(0), the other counters left alone).  It
+// stands at the head of the output pass: a load still pending there (spill reloads of the single evaluation of `start` /
+// `reset` / `refresh`, the status read-back of `refresh`) otherwise gets the compiler's own wait somewhere between the
+// output stores, on every path, and that wait also waits for every store issued before it.
+#ifdef JM_HOST_EMU
+#define JM_OUTPUT_PASS_BEGIN() ((void)0)
+#define JM_WAIT_VMEM() ((void)0)
+#else
+#define JM_OUTPUT_PASS_BEGIN() asm volatile("; quad output pass" ::: "memory")
+// (gfx9 encoding of the s_waitcnt immediate, which gfx950 uses: vmcnt = bits 3:0 and 15:14 -> 0, expcnt = bits 6:4 -> 7 and
+// lgkmcnt = bits 11:8 -> 15, i.e. "do not wait" for the last two; the libraries are built for gfx950 only)
+#define JM_WAIT_VMEM() __builtin_amdgcn_s_waitcnt(0x0F70)
+#endif
+
 namespace jm
 {
 // ---------------------------------------------------------------- limb table layout (scalars)
@@ -759,8 +776,20 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
     (void)te;   // time of this dynamics evaluation: read by the process forces (GEN)
     // velocities / commands: registers for short limbs, re-read from the stage buffer for long ones
     using RW = QRows<Tp>;
-    auto vlq = [&](int s) -> T { if constexpr (RW::LONG) return S_.getl(RW::KVL + s); else return vl_[s]; };
-    auto vbq = [&](int i) -> T { if constexpr (RW::LONG) return S_.getb(RW::KVB + i); else return vb_[i]; };
+    // (the float64 output pass of short limbs reads the velocities from the rows of the committed state as well: nothing
+    // of the state stays live across its body walk.  The float32 kernels keep them in registers: their walk needs half
+    // as many, and the extra LDS reads only cost them spill slots -- biped, W = 1: 211 -> 220.)
+    constexpr bool ROWS_V = !DYN && sizeof(T) == 8;
+    auto vlq = [&](int s) -> T {
+        if constexpr (RW::LONG) return S_.getl(RW::KVL + s);
+        else if constexpr (ROWS_V) return S_.getl(RW::V0L + s);
+        else return vl_[s];
+    };
+    auto vbq = [&](int i) -> T {
+        if constexpr (RW::LONG) return S_.getb(RW::KVB + i);
+        else if constexpr (ROWS_V) return S_.getb(RW::V0B + i);
+        else return vb_[i];
+    };
     auto cmdlq = [&](int s) -> T { return S_.getl(RW::CMDL + s); };
     auto cmdbq = [&](int t) -> T { return S_.getb(RW::CMDB + t); };
     // compile-time: the three non-emitting evaluations of an RK4 step carry no output code at all,
@@ -1343,10 +1372,21 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
             // as their total, follow from  sum_bodies (Y a + v x* h) = f_root + sum f_ext - sum_bodies Y agf1,  and the
             // last sum is (m_tot agf1.l, mc_tot x agf1.l) unless the gravity has an angular part (uniform test).
             const bool has_gw = gw.x != T(0) || gw.y != T(0) || gw.z != T(0);
-            // limb: wind the acceleration up to the tip
+            // The root placement, the gravity field in root coordinates and the root twist are read by the end of the walk
+            // only: they are re-derived there from the rows of the committed state (the same expressions on the same
+            // inputs as above) instead of staying live across the limb walk, which needs every register it can get.
+            // (GEN kernels are excepted: the applied wrenches of their limb walk read the first `R1`, which stays live
+            // there -- they run one wave per SIMD with twice the registers: ANYmal's does not spill at all, Atlas' spills less than before.)
+            JM_REFRESH();
+            auto root_placement = [&]() -> SE3<T> {
+                return {quat_to_matrix(S_.getb(RW::Q0B + 3), S_.getb(RW::Q0B + 4), S_.getb(RW::Q0B + 5), S_.getb(RW::Q0B + 6)),
+                        V3<T>{S_.getb(RW::Q0B + 0), S_.getb(RW::Q0B + 1), S_.getb(RW::Q0B + 2)}};
+            };
+            auto gravity_field = [&]() -> Sp<T> { return actinv_motion(root_placement(), Sp<T>{-g, -gw}); };
+            // limb: wind the velocity and the acceleration up to the tip
             Sp<T> acur = ap;
+            Sp<T> vrun = vp;
             {
-                Sp<T> vrun = vp;
                 static_for<0, N>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     V3<T> a_s, p_s;
@@ -1367,20 +1407,20 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
             T ms = T(0), ekin = T(0), erot = T(0);
             V3<T> mcs = zero3<T>();
             {
-                Sp<T> vcur = vtip;
-                M3<T> Rcur = Rtip;
-                V3<T> pcur = ptip;
+                // (the wind-up has arrived at the tip: its placement and velocity are the ones the kinematics above found)
+                Sp<T> vcur = vrun;
+                M3<T> Rcur = Rw;
+                V3<T> pcur = pw;
                 static_rfor<0, N>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     constexpr int o = s * Q::QJ;
-                    if constexpr (!UNWIND) { Rcur = Rs[s]; pcur = ps[s]; }
                     const RBI<T> Y = rbi_placed(Rcur, pcur, ma.rbi(GEN ? limb_joint_of(sc) : 0, LT.rbi(o + Q::J_RBI)));
                     const V3<T> a = limb_axis_root<T, Tp, s>(LT, Rcur);
                     const Sp<T> S = {cross(pcur, a), a};
                     const Sp<T> h = rbi_mul(Y, vcur);
                     hs = hs + h;
                     fjs = fjs + cross_mf(vcur, h) + rbi_mul(Y, acur);
-                    if (has_gw) Gs = Gs + rbi_mul(Y, agf1);
+                    if (has_gw) Gs = Gs + rbi_mul(Y, gravity_field());
                     if constexpr (s == N - 1) fjs = fjs - fext;
                     if constexpr (GEN)
                         if (A.applied_k > 0)
@@ -1408,6 +1448,12 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
             T mtot = X::quad_sum(ms);
             V3<T> mctot = {X::quad_sum(mcs.x), X::quad_sum(mcs.y), X::quad_sum(mcs.z)};
             ekin = X::quad_sum(ekin); erot = X::quad_sum(erot);
+            // root quantities of the trunk walk and of the closing block
+            const SE3<T> M1 = root_placement();
+            const Sp<T> agf1x = actinv_motion(M1, Sp<T>{-g, -gw});
+            const Sp<T> v1x = {{S_.getb(RW::V0B + 0), S_.getb(RW::V0B + 1), S_.getb(RW::V0B + 2)},
+                               {S_.getb(RW::V0B + 3), S_.getb(RW::V0B + 4), S_.getb(RW::V0B + 5)}};
+            const Sp<T> at0x = agf1x + Sp<T>{{ddqb[0], ddqb[1], ddqb[2]}, {ddqb[3], ddqb[4], ddqb[5]}};
             Sp<T> fjT[NT];
             static_for<0, NT>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
@@ -1422,7 +1468,7 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
                 constexpr int t = decltype(tc)::value;
                 constexpr int j = Tp::trunk_joint[t];
                 SE3<T> Xt = {ident3<T>(), zero3<T>()};
-                Sp<T> vt = v1r, att = at0;
+                Sp<T> vt = v1x, att = at0x;
                 RBI<T> Y = ma.rbi(j, ld_rbi<T>(P, L::JOINT + j * L::JSTRIDE + 12));
                 if constexpr (t > 0)
                 {
@@ -1433,15 +1479,15 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
                 const Sp<T> h = rbi_mul(Y, vt);
                 htot = htot + h;
                 fjT[t] = fjT[t] + cross_mf(vt, h) + rbi_mul(Y, att);
-                if (has_gw) Gtot = Gtot + rbi_mul(Y, agf1);
+                if (has_gw) Gtot = Gtot + rbi_mul(Y, agf1x);
                 if constexpr (GEN)
                     if (A.applied_k > 0)
                     {
                         Sp<T> w;
-                        if constexpr (t == 0) w = applied_root_wrench(A, R1, Bg, rg, te);
+                        if constexpr (t == 0) w = applied_root_wrench(A, M1.R, Bg, rg, te);
                         else
                         {
-                            w = applied_wrench_on(A, j, R1, Xt.R, Xt.p, Bg, rg, te);
+                            w = applied_wrench_on(A, j, M1.R, Xt.R, Xt.p, Bg, rg, te);
                             if (applied_out && lead) put6(A.f_external, B32, r32, 6 * j, wrench_to_joint(Xt.R, Xt.p, w));
                         }
                         fjT[t] = fjT[t] - w;
@@ -1464,17 +1510,16 @@ JM_DEV void quad_eval(CPtr<T> P, const LimbTable<T> & LT, const BatchArgs<T> & A
                 if (want_energy)
                 {
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) erot += P[L::ROTOR + Tp::idx_v[1] + i] * vb_[i] * vb_[i];
+                    for (int i = 0; i < 6; ++i) erot += P[L::ROTOR + Tp::idx_v[1] + i] * S_.getb(RW::V0B + i) * S_.getb(RW::V0B + i);
                     A.energy[r32] = T(0.5) * ekin + T(0.5) * erot;
-                    A.energy[B32 + r32] = -(dot(R1 * mctot, g) + mtot * dot(p1, g));
+                    A.energy[B32 + r32] = -(dot(M1.R * mctot, g) + mtot * dot(M1.p, g));
                 }
                 if (A.centroidal)
                 {
-                    if (!has_gw) Gtot = {mtot * agf1.l, cross(mctot, agf1.l)};
+                    if (!has_gw) Gtot = {mtot * agf1x.l, cross(mctot, agf1x.l)};
                     const Sp<T> fBtot = fjT[0] + fxtot - Gtot;
-                    const SE3<T> M1 = {R1, p1};
                     const V3<T> c1 = rcp_(mtot) * mctot;
-                    const V3<T> com0 = R1 * c1 + p1;
+                    const V3<T> com0 = M1.R * c1 + M1.p;
                     Sp<T> hg = act_force(M1, htot), dhg = act_force(M1, fBtot);
                     hg.a = hg.a + cross(hg.l, com0);
                     dhg.a = dhg.a + cross(dhg.l, com0);
@@ -1988,6 +2033,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         }
     };
     unsigned rr = r32;
+    int status_before = 0;   // MODE_REFRESH ORs into the status row: the one global load of the epilogue
     if constexpr (QCON)
     {
         // constraint contact model: ONE call site of the (large) constrained evaluation, emitting or not at run time
@@ -2081,7 +2127,13 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
     }
     if (A.mode != MODE_DYNAMICS)
     {
-        JM_REFRESH();
+        JM_OUTPUT_PASS_BEGIN();
+        if (A.mode == MODE_REFRESH && A.status && lead) status_before = A.status[r32];
+        // Nothing may be in flight when the first output store is issued: a wait for a load that the compiler places between
+        // the stores also waits for every store before it.  The step path has nothing pending here (its commit stores were
+        // issued before the last evaluation); the single evaluation of the other modes reloads spilled lane offsets, and
+        // `refresh` has just read the status row back.
+        JM_WAIT_VMEM();
         rr = r32;
         JM_OPAQUE(rr);
         // the (committed) state is re-read from the stage buffer: kept in registers it would be live across the
@@ -2101,7 +2153,8 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
         if (A.mode != MODE_DYNAMICS)
         {
             const int stq = X::quad_or(status);
-            if (A.status && lead) A.status[rr] = (A.mode == MODE_REFRESH) ? (A.status[rr] | stq) : stq;
+            if constexpr (QCON) { if (A.status && lead) A.status[rr] = (A.mode == MODE_REFRESH) ? (A.status[rr] | stq) : stq; }
+            else if (A.status && lead) A.status[rr] = status_before | stq;
             if constexpr (GEN && PH == 0)
                 if (stepping && lead && A.proc_off > 0) proc_block(A).lane_time()[rr] = tl;
             // (spring-damper kernels: the output pass above has written the extra terms already)
