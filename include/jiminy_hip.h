@@ -1042,6 +1042,102 @@ int32_t jm_trajectory_plan_destroy(jm_trajectory_plan * plan);
 int32_t jm_block_trajectory_state(const jm_trajectory_plan * plan, int32_t dtype, int64_t batch_size, const jm_trajectory_io * io,
                                   void * stream);
 
+/* ---- Centroidal quantities of an arbitrary state: the centre of mass, the centroidal momentum and its time derivative from
+ * any `(q, v, a)` -- what the reference computes on the CPU with `pin.computeCentroidalMomentumTimeVariation`
+ * (python/jiminy_py/src/jiminy_py/dynamics.py:496-499, reached from `StateQuantity.refresh`,
+ * python/gym_jiminy/common/gym_jiminy/common/bases/quantities.py:1494-1518) for the state of a reference trajectory; batched,
+ * one lane = one environment, one launch per call.  New symbols only: no existing structure or signature changed with them.
+ * jm_centroidal_desc: the plan (host arrays, copied by jm_centroidal_plan_create) of the NOMINAL model.  Per body the walk from
+ *   the universe to the body's joint frame as a list of segments `body_seg_start[b] .. body_seg_start[b + 1] - 1` in the tables
+ *   of jm_frames_desc (kinds, rows, placements, axes; at most 256 per body), and its `body_mass`, `body_com` (in the joint frame)
+ *   and `body_inertia` (about the centre of mass, joint-frame axes: xx xy xz yy yz zz).  jm_centroidal_plan_create validates the
+ *   description like jm_frames_plan_create (JM_EINVAL + jm_last_error, before any device call) and also rejects constants
+ *   that are not finite, a negative mass and a total mass that is not positive.  ≙ the inertias of `pinocchio_model`.
+ * jm_block_centroidal_state: on the lanes of `lane_mask` (device, uint8 `[B]`; NULL: every lane; other lanes are not touched)
+ *   writes `centroidal` `[15][B]` in the row layout of JM_F_CENTROIDAL: com (3), hg (6: linear then angular, about the centre
+ *   of mass, world axes), dhg (6: `I a + v x* I v` summed over the bodies -- no gravity, no external forces, `fBody[0]` of
+ *   `computeExtraTerms`, core/src/engine/engine.cc:800-905).  `q` `[nq][B]`, `v`, `a` `[nv][B]` in pinocchio's convention
+ *   (spatial, in the joint's local frame); `a` may be NULL: the dhg rows are then written as zeros.  The centre-of-mass
+ *   velocity is `hg_linear / mass`.  Allocates, copies and synchronises nothing; no argument changes from call to call, so
+ *   the launch can be part of a captured graph. */
+typedef struct jm_centroidal_desc
+{
+    int32_t n_bodies;
+    int32_t nq;                         /* rows of q: the range of seg_q_index */
+    int32_t nv;                         /* rows of v, a: the range of seg_v_index */
+    int32_t njoints;                    /* the range of seg_joint */
+    const int32_t * body_seg_start;     /* [n_bodies + 1], ascending, last = n_seg */
+    int32_t n_seg;
+    const int32_t * seg_kind;           /* [n_seg] */
+    const int32_t * seg_joint;          /* [n_seg], -1 where seg_kind is 0 */
+    const int32_t * seg_q_index;        /* [n_seg], -1 where seg_kind is 0 */
+    const int32_t * seg_v_index;        /* [n_seg], -1 where seg_kind is 0 */
+    const double * seg_rot;             /* [n_seg][9] */
+    const double * seg_trans;           /* [n_seg][3] */
+    const double * seg_axis;            /* [n_seg][3] */
+    const double * body_mass;           /* [n_bodies] */
+    const double * body_com;            /* [n_bodies][3] */
+    const double * body_inertia;        /* [n_bodies][6] */
+} jm_centroidal_desc;
+typedef struct jm_centroidal_plan jm_centroidal_plan;
+int32_t jm_centroidal_plan_create(const jm_centroidal_desc * desc, jm_centroidal_plan ** out);
+int32_t jm_centroidal_plan_destroy(jm_centroidal_plan * plan);
+int32_t jm_block_centroidal_state(const jm_centroidal_plan * plan, int32_t dtype, int64_t batch_size, const void * q,
+                                  const void * v, const void * a, const uint8_t * lane_mask, void * centroidal, void * stream);
+
+/* ---- Tracking rewards on balance quantities: a quantity on the true state and on the state of the reference trajectory, and
+ * the radial basis function of their difference -- the `TrackingQuantityReward` family
+ * (python/gym_jiminy/common/gym_jiminy/common/compositions/generic.py:64-122); batched, one lane = one environment, one launch per
+ * refresh.  New symbols only: no existing structure or signature changed with them.  Terms, in the order of the rows of
+ * `rewards` and of `cutoff`: 0 base height ≙ `TrackingBaseHeightReward` (compositions/locomotion.py:33-51; `compute_height`,
+ * quantities/locomotion.py:88-97: root z minus the lowest contact frame z of `pose`); 1 odometry velocity ≙
+ * `TrackingBaseOdometryVelocityReward` (:54-72; rows (0, 1, 5) of `quat_apply(quat_no_yaw, v_avg)` of the root column, which is
+ * LOCAL: quantities/locomotion.py:281-288, :329-333); 2 capture point ≙ `TrackingCapturePointReward` (:123-143; the `dcm` of two
+ * jm_block_locomotion launches, LOCAL); 3 joint positions ≙ `TrackingActuatedJointPositionsReward`
+ * (compositions/generic.py:125-150).
+ * jm_trackrewards_desc: the columns of 'root_joint' and of the contact frames in the tensors of the true and of the reference
+ *   frame kinematics block (`n_frames`, `n_frames_reference` columns; 0: that side has none), and the number of motors.
+ *   jm_trackrewards_plan_create validates it (JM_EINVAL + jm_last_error, before any device call).
+ * jm_trackrewards_io: the device pointers of one launch, each or NULL.  Outputs: `value`, `reference` `[6 + n_motors][B]` (the
+ *   true and the reference side concatenated: height 1, odometry velocity 3, capture point 2, joint positions n_motors),
+ *   `rewards` `[4][B]` = `radial_basis_function(value - reference, cutoff, 2)` (compositions/mixin.py:26-66).
+ * jm_block_tracking_rewards: `cutoff[4]` (host); a term whose cutoff is not positive or whose inputs are NULL is skipped and
+ *   its rows are not written.  Lanes outside `lane_mask` (uint8 `[B]`, NULL: every lane) are not touched.  No argument
+ *   changes from step to step, so the launch can be part of a captured graph. */
+typedef struct jm_trackrewards_desc
+{
+    int32_t n_contacts;
+    int32_t n_motors;
+    int32_t n_frames;
+    int32_t root_column;
+    const int32_t * contact_column;             /* [n_contacts] */
+    int32_t n_frames_reference;
+    int32_t root_column_reference;
+    const int32_t * contact_column_reference;   /* [n_contacts] */
+} jm_trackrewards_desc;
+typedef struct jm_trackrewards_io
+{
+    const void * pose;
+    const void * pose_reference;
+    const void * v_avg;
+    const void * quat_no_yaw;
+    const void * v_avg_reference;
+    const void * quat_no_yaw_reference;
+    const void * dcm;
+    const void * dcm_reference;
+    const void * position;
+    const void * position_reference;
+    const uint8_t * lane_mask;
+    void * value;
+    void * reference;
+    void * rewards;
+} jm_trackrewards_io;
+typedef struct jm_trackrewards_plan jm_trackrewards_plan;
+int32_t jm_trackrewards_plan_create(const jm_trackrewards_desc * desc, jm_trackrewards_plan ** out);
+int32_t jm_trackrewards_plan_destroy(jm_trackrewards_plan * plan);
+int32_t jm_block_tracking_rewards(const jm_trackrewards_plan * plan, int32_t dtype, int64_t batch_size, const jm_trackrewards_io * io,
+                                  const double * cutoff, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

@@ -194,6 +194,35 @@ class TrajectoryIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in TRAJECTORY_IO_FIELDS]
 
 
+class TrackRewardsDesc(C.Structure):
+    """jm_trackrewards_desc: the plan of the tracking rewards (jiminy_amd.trackrewards builds it)."""
+    _fields_ = [
+        ("n_contacts", C.c_int32), ("n_motors", C.c_int32),
+        ("n_frames", C.c_int32), ("root_column", C.c_int32), ("contact_column", _pi),
+        ("n_frames_reference", C.c_int32), ("root_column_reference", C.c_int32), ("contact_column_reference", _pi),
+    ]
+
+
+TRACKREWARDS_IO_FIELDS = ("pose", "pose_reference", "v_avg", "quat_no_yaw", "v_avg_reference", "quat_no_yaw_reference", "dcm",
+                          "dcm_reference", "position", "position_reference", "lane_mask", "value", "reference", "rewards")
+
+
+class TrackRewardsIO(C.Structure):
+    """jm_trackrewards_io: the device pointers of one launch of jm_block_tracking_rewards, each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in TRACKREWARDS_IO_FIELDS]
+
+
+class CentroidalDesc(C.Structure):
+    """jm_centroidal_desc: the plan of the centroidal quantities of a state (jiminy_amd.centroidal builds it)."""
+    _fields_ = [
+        ("n_bodies", C.c_int32), ("nq", C.c_int32), ("nv", C.c_int32), ("njoints", C.c_int32),
+        ("body_seg_start", _pi),
+        ("n_seg", C.c_int32), ("seg_kind", _pi), ("seg_joint", _pi), ("seg_q_index", _pi), ("seg_v_index", _pi),
+        ("seg_rot", _pd), ("seg_trans", _pd), ("seg_axis", _pd),
+        ("body_mass", _pd), ("body_com", _pd), ("body_inertia", _pd),
+    ]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

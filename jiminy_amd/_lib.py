@@ -59,6 +59,8 @@ ABI_SYMBOLS = (
     "jm_footposes_plan_create", "jm_footposes_plan_destroy", "jm_block_foot_poses",
     "jm_tracking_plan_create", "jm_tracking_plan_destroy", "jm_block_tracking",
     "jm_trajectory_plan_create", "jm_trajectory_plan_destroy", "jm_block_trajectory_state",
+    "jm_centroidal_plan_create", "jm_centroidal_plan_destroy", "jm_block_centroidal_state",
+    "jm_trackrewards_plan_create", "jm_trackrewards_plan_destroy", "jm_block_tracking_rewards",
 )
 
 
@@ -140,6 +142,12 @@ class HipLibrary:
         L.jm_trajectory_plan_create.argtypes = [C.POINTER(_abi.TrajectoryDesc), C.POINTER(vp)]
         L.jm_trajectory_plan_destroy.argtypes = [vp]
         L.jm_block_trajectory_state.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrajectoryIO), vp]
+        L.jm_centroidal_plan_create.argtypes = [C.POINTER(_abi.CentroidalDesc), C.POINTER(vp)]
+        L.jm_centroidal_plan_destroy.argtypes = [vp]
+        L.jm_block_centroidal_state.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp]
+        L.jm_trackrewards_plan_create.argtypes = [C.POINTER(_abi.TrackRewardsDesc), C.POINTER(vp)]
+        L.jm_trackrewards_plan_destroy.argtypes = [vp]
+        L.jm_block_tracking_rewards.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrackRewardsIO), dp, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

@@ -52,6 +52,16 @@ specification: tests/golden/ref_tracking.npz.
 selection and time offset; time modes, bisection, Lie-group interpolation, wrap odometry): the reference side of the four
 blocks above.  One HIP launch per query (csrc/jm_trajectory.h) driven by a plan that jiminy_amd/trajectory.py builds;
 specification: tests/golden/ref_trajectory.npz.
+
+`CentroidalState` gives the centre of mass, the centroidal momentum and its time derivative of any state `(q, v, a)` -- the
+state of a reference trajectory, for which the physics kernels leave no `centroidal` rows -- on the nominal model: one HIP
+launch per refresh (csrc/jm_centroidal.h) driven by a plan that jiminy_amd/centroidal.py builds; specification: the oracle's
+`centroidal` rows.  `LocomotionQuantities(state=(q, centroidal))` evaluates the balance quantities on it.
+
+`TrackingRewards` gives the tracking rewards on balance quantities (base height, odometry velocity, capture point, actuated
+joint positions): each quantity on the true side and on the reference side and the radial basis function of their difference,
+from the tensors of the blocks above.  One HIP launch per refresh (csrc/jm_trackrewards.h) driven by a plan that
+jiminy_amd/trackrewards.py builds; specification: tests/golden/ref_tracking_rewards.npz.
 """
 from __future__ import annotations
 
@@ -528,6 +538,92 @@ class FrameKinematics:
                 pass
 
 
+class CentroidalState:
+    """The centroidal quantities of a state other than the engine's own: `centroidal` `[15][B]` in the row layout of the
+    engine's `centroidal` field -- com (3), hg (6: linear then angular, about the centre of mass, world axes), dhg (6) -- from
+    `state=(q, v, a)`, `[rows][B]` tensors in pinocchio's convention (`ReferenceTrajectory.q` / `.v` / `.a`); `a` may be None:
+    the dhg rows stay zero.  ≙ `pin.computeCentroidalMomentumTimeVariation` on the state of a trajectory
+    (jiminy_py/dynamics.py:496-499, reached from `StateQuantity.refresh`, bases/quantities.py:1494-1518): dhg holds no gravity
+    and no external force.  The model is the nominal one, never the lane's biased one: the reference evaluates a trajectory on
+    the trajectory's own robot.  The centre-of-mass velocity is `centroidal[3:6] / mass`.
+
+    `refresh()` evaluates every lane, `reset(lane_mask)` the masked ones (every lane without a mask) and keeps the others bit
+    for bit.  Each is one launch on the engine's stream, without allocation, copy or synchronisation; the tensor never changes
+    identity."""
+
+    def __init__(self, engine, state) -> None:
+        import ctypes as C
+        import os
+
+        from . import _abi, centroidal
+        if os.environ.get("JIMINY_AMD_TENSOR_BLOCKS", "0") == "1":
+            raise NotImplementedError("the centroidal state has no tensor-program form (JIMINY_AMD_TENSOR_BLOCKS=1): "
+                                      "the evaluation exists as the HIP kernel only")
+        q, v, a = state
+        model, B = engine.model, engine.batch_size
+        for name, t, rows in (("q", q, model.nq), ("v", v, model.nv), ("a", a, model.nv)):
+            if t is None and name == "a":
+                continue
+            if t is None or tuple(t.shape) != (rows, B):
+                raise ValueError(f"state {name} must have shape ({rows}, {B})")
+        self._C = C
+        self._eng, self._state = engine, (q, v, a)
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.plan = centroidal.build_plan(model)
+        self.mass = self.plan.mass
+        self.has_acceleration = a is not None
+        self.centroidal = torch.zeros((centroidal.ROWS, B), dtype=engine.dtype, device=engine.device)
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_centroidal_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        xyz = ("X", "Y", "Z")
+        return {"centroidal": [f"Com.{e}" for e in xyz] + [f"{h}.{k}{e}" for h in ("Momentum", "MomentumRate") for k in ("Lin", "Ang")
+                                                             for e in xyz]}
+
+    def _vp(self, t: Optional[torch.Tensor]):
+        if t is None:
+            return None
+        _check_block_tensor(self._eng, t)
+        return self._C.c_void_p(t.data_ptr())
+
+    def _launch(self, mask: Optional[torch.Tensor]) -> None:
+        eng = self._eng
+        q, v, a = self._state
+        self._check(self._L.jm_block_centroidal_state(
+            self._plan, self._dtype, eng.batch_size, self._vp(q), self._vp(v), self._vp(a),
+            None if mask is None else self._C.c_void_p(mask.data_ptr()), self._vp(self.centroidal), eng._stream()))
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The quantities at the state tensors on the masked lanes (every lane without a mask); the other lanes keep every
+        bit."""
+        eng = self._eng
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        self._launch(mask)
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream: `centroidal` at the state tensors."""
+        self._launch(None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_centroidal_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
 LOCOMOTION_SCALARS = ("force_vertical_max", "ground_distance_min", "reward_momentum", "reward_friction")
 
 
@@ -560,11 +656,18 @@ class LocomotionQuantities:
     `average=True` unless `momentum=False`; refresh it first.  The force quantities need the constraint contact model
     (`forces=False` leaves them out).  `refresh()` is one launch on the engine's stream, without allocation, copy or
     synchronisation; `reset(lane_mask)` evaluates the masked lanes (every lane without a mask) at the state the engine's
-    `start` / `reset_lanes` wrote and keeps the others bit for bit.  The tensors never change identity."""
+    `start` / `reset_lanes` wrote and keeps the others bit for bit.  The tensors never change identity.
+
+    `state=(q, centroidal)`: the quantities of another state than the engine's -- `QuantityEvalMode.REFERENCE`.  `q` `[nq][B]`
+    (`ReferenceTrajectory.q`) and `centroidal`, a `CentroidalState` block of that state or its `[15][B]` tensor, are read
+    instead of the engine's fields; `frames` must be a `FrameKinematics(state=...)` block of the same state; the lane's biased
+    model is not applied.  A recorded trajectory carries no constraint multipliers: `forces=True` raises.  Where the state has
+    no acceleration (`CentroidalState` built with `a` None), `zmp` is None: the reference's `ZeroMomentPoint.initialize` raises
+    in that case."""
 
     def __init__(self, engine, frames: "FrameKinematics", *, foot_frame_names="auto", zmp_reference_frame="LOCAL",
                  dcm_reference_frame="LOCAL", momentum_cutoff: Optional[float] = None, friction_cutoff: Optional[float] = None,
-                 momentum: bool = True, forces: bool = True) -> None:
+                 momentum: bool = True, forces: bool = True, state=None) -> None:
         import ctypes as C
 
         from . import _abi, locomotion
@@ -572,7 +675,22 @@ class LocomotionQuantities:
         model = engine.model
         if not model.has_freeflyer:
             raise ValueError("Only legged robot with floating base are supported: the model has no free-flyer.")
-        if "centroidal" not in engine._fields:
+        self._state, has_acceleration = None, True
+        if state is not None:
+            if forces:
+                raise NotImplementedError("the contact force quantities of a reference state: a recorded trajectory carries no "
+                                          "constraint multipliers (`State.lambda_c`); pass forces=False")
+            q, centroidal = state
+            if isinstance(centroidal, CentroidalState):
+                has_acceleration, centroidal = centroidal.has_acceleration, centroidal.centroidal
+            if tuple(q.shape) != (model.nq, engine.batch_size):
+                raise ValueError(f"state q must have shape ({model.nq}, {engine.batch_size})")
+            if tuple(centroidal.shape) != (15, engine.batch_size):
+                raise ValueError(f"state centroidal must have shape (15, {engine.batch_size})")
+            if frames._state is None or frames._state[0] is not q:
+                raise ValueError("the frame kinematics block must be built on the same state: FrameKinematics(state=(q, v))")
+            self._state = (q, centroidal)
+        if state is None and "centroidal" not in engine._fields:
             raise ValueError("the locomotion quantities read the 'centroidal' output of the engine: build it with "
                              "extra_outputs=(..., 'centroidal') or call enable_output('centroidal')")
         if frames._eng is not engine:
@@ -610,6 +728,8 @@ class LocomotionQuantities:
         B, nc = engine.batch_size, self.plan.n_contacts
         new = lambda *shape: torch.zeros((*shape, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
         self.com, self.vcom, self.odom_pose, self.zmp, self.dcm, self.scalars = new(3), new(3), new(3), new(2), new(2), new(4)
+        if not has_acceleration:
+            self.zmp = None
         self.h_angular = new(3) if self.momentum else None
         self.contact_force_rel = new(6, nc) if self.forces else None
         self.foot_force_vertical = new(self.plan.n_feet) if self.forces else None
@@ -652,8 +772,12 @@ class LocomotionQuantities:
             if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
                 raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
             return t.data_ptr()
-        io.centroidal, io.q_root = ptr(eng.field("centroidal")), ptr(eng.field("q")[self._q_row:self._q_row + 7])
-        io.model_lane = ptr(eng._fields.get("model_lane"))
+        if self._state is not None:
+            q, centroidal = self._state
+            io.centroidal, io.q_root, io.model_lane = ptr(centroidal), ptr(q[self._q_row:self._q_row + 7]), None
+        else:
+            io.centroidal, io.q_root = ptr(eng.field("centroidal")), ptr(eng.field("q")[self._q_row:self._q_row + 7])
+            io.model_lane = ptr(eng._fields.get("model_lane"))
         io.con_lambda = io.con_flags = None
         if self.forces:
             # (the constraint state of the engine exists once the constraint contact model is selected)
@@ -1368,6 +1492,146 @@ def integrate_zoh(state: torch.Tensor, state_min: torch.Tensor, state_max: torch
     state[2].copy_((vel - v_prev) / dt)
     state[1].copy_(vel)
     state[0].copy_(position + dt * vel)
+
+
+TRACKING_REWARD_TERMS = ("base_height", "odometry_velocity", "capture_point", "joint_positions")
+
+
+def tracking_rewards_fieldnames(motor_names):
+    """Names of the rows of the tensors of a `TrackingRewards` block (`value` and `reference` share theirs)."""
+    rows = ["BaseHeight", "OdometryVelocity.X", "OdometryVelocity.Y", "OdometryVelocity.Yaw", "CapturePoint.X", "CapturePoint.Y"]
+    rows += [f"{n}.Position" for n in motor_names]
+    return {"value": rows, "reference": list(rows), "rewards": [f"reward_{t}" for t in TRACKING_REWARD_TERMS]}
+
+
+class TrackingRewards:
+    """The tracking rewards of the reference's composition layer on balance quantities per lane: a quantity in
+    `QuantityEvalMode.TRUE` against the same quantity in `QuantityEvalMode.REFERENCE` ≙ `TrackingQuantityReward`
+    (compositions/generic.py:64-122).  Terms (`TRACKING_REWARD_TERMS`, the rows of `rewards` `[4][B]`): the base height ≙
+    `TrackingBaseHeightReward` (compositions/locomotion.py:33-51), root z minus the lowest contact frame z of the `pose` of
+    `frames` / `reference_frames`; the odometry velocity ≙ `TrackingBaseOdometryVelocityReward` (:54-72), rows (0, 1, 5) of the
+    step-average velocity of 'root_joint' turned by its `quat_no_yaw` (both blocks with `average=True`, the column LOCAL); the
+    capture point ≙ `TrackingCapturePointReward` (:123-143), the `dcm` of `locomotion` / `reference_locomotion`, both built
+    with `dcm_reference_frame="LOCAL"`; the joint positions ≙ `TrackingActuatedJointPositionsReward`
+    (compositions/generic.py:125-150), `actuation.position` against `trajectory.position`.  `value` and `reference`
+    `[6 + n_motors][B]` hold the two sides concatenated (height 1, velocity 3, capture point 2, positions), `rewards` is
+    `radial_basis_function(value - reference, cutoff, 2)`.  A term whose cutoff is None is skipped: its rows stay zero.
+
+    `refresh()` is one launch on the engine's stream behind the refresh of every block it reads, `reset(lane_mask)` the same
+    on the masked lanes (every lane without a mask), the others keeping every bit.  No allocation, copy or synchronisation;
+    the tensors never change identity."""
+
+    def __init__(self, engine, *, frames=None, reference_frames=None, locomotion=None, reference_locomotion=None, actuation=None,
+                 trajectory=None, base_height_cutoff: Optional[float] = None, odometry_velocity_cutoff: Optional[float] = None,
+                 capture_point_cutoff: Optional[float] = None, joint_positions_cutoff: Optional[float] = None) -> None:
+        import ctypes as C
+        import os
+
+        from . import _abi, trackrewards
+        from . import frames as frames_
+        if os.environ.get("JIMINY_AMD_TENSOR_BLOCKS", "0") == "1":
+            raise NotImplementedError("the tracking rewards have no tensor-program form (JIMINY_AMD_TENSOR_BLOCKS=1): "
+                                      "they exist as the HIP kernel only")
+        cutoffs = (base_height_cutoff, odometry_velocity_cutoff, capture_point_cutoff, joint_positions_cutoff)
+        for cutoff in cutoffs:
+            if cutoff is not None and not float(cutoff) > 0.0:
+                raise ValueError("a reward cutoff must be positive")
+        for blk in (frames, reference_frames, locomotion, reference_locomotion, actuation, trajectory):
+            if blk is not None and blk._eng is not engine:
+                raise ValueError("a block the tracking rewards read belongs to another engine")
+        if (base_height_cutoff is not None or odometry_velocity_cutoff is not None) and (frames is None or reference_frames is None):
+            raise ValueError("the base height and the odometry velocity read the frame kinematics blocks of both sides: "
+                             "pass frames and reference_frames")
+        if odometry_velocity_cutoff is not None:
+            for blk in (frames, reference_frames):
+                if not blk.average:
+                    raise ValueError("the odometry velocity reads the step average of the root frame: build both frame "
+                                     "kinematics blocks with average=True")
+                if blk.plan.modes[blk.index("root_joint")] != frames_.LOCAL:
+                    raise ValueError("the odometry velocity reads the LOCAL step-average velocity of 'root_joint': a frame "
+                                     "kinematics block holds it in another reference frame")
+        if capture_point_cutoff is not None:
+            if locomotion is None or reference_locomotion is None:
+                raise ValueError("the capture point reads the locomotion blocks of both sides: pass locomotion and "
+                                 "reference_locomotion")
+            for blk in (locomotion, reference_locomotion):
+                if blk.plan.arrays["dcm_frame"] != frames_.LOCAL:
+                    raise ValueError("the capture point is tracked in the odometry frame: build both locomotion blocks with "
+                                     "dcm_reference_frame='LOCAL'")
+        if joint_positions_cutoff is not None and (actuation is None or trajectory is None or trajectory.position is None):
+            raise ValueError("the joint positions read actuation.position and trajectory.position: pass actuation and a "
+                             "trajectory built with it")
+        n_motors = 0 if actuation is None else int(actuation.position.shape[0])
+        self.plan = trackrewards.build_plan(engine.model, None if frames is None else frames.frame_names,
+                                            None if reference_frames is None else reference_frames.frame_names, n_motors)
+        self._C = C
+        self._eng = engine
+        self._blocks = (frames, reference_frames, locomotion, reference_locomotion, actuation, trajectory)
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.cutoffs = tuple(None if c is None else float(c) for c in cutoffs)
+        self._cutoff = (C.c_double * 4)(*[c or 0.0 for c in self.cutoffs])
+        B = engine.batch_size
+        new = lambda rows: torch.zeros((rows, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
+        self.value, self.reference, self.rewards = new(self.plan.rows), new(self.plan.rows), new(4)
+        self._io = _abi.TrackRewardsIO()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_trackrewards_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        return tracking_rewards_fieldnames([m.name for m in self._eng.model.motors][:self.plan.n_motors])
+
+    def reward(self, term: str) -> torch.Tensor:
+        """The row of `rewards` of a term of `TRACKING_REWARD_TERMS`."""
+        return self.rewards[TRACKING_REWARD_TERMS.index(term)]
+
+    def _launch(self, mask: Optional[torch.Tensor]) -> None:
+        eng, io = self._eng, self._io
+        frames, reference_frames, locomotion, reference_locomotion, actuation, trajectory = self._blocks
+
+        def ptr(t: Optional[torch.Tensor]):
+            if t is None:
+                return None
+            _check_block_tensor(eng, t)
+            return t.data_ptr()
+        get = lambda blk, name: None if blk is None else ptr(getattr(blk, name))      # noqa: E731
+        io.pose, io.pose_reference = get(frames, "pose"), get(reference_frames, "pose")
+        io.v_avg, io.quat_no_yaw = get(frames, "average_velocity"), get(frames, "quat_no_yaw")
+        io.v_avg_reference, io.quat_no_yaw_reference = get(reference_frames, "average_velocity"), get(reference_frames, "quat_no_yaw")
+        io.dcm, io.dcm_reference = get(locomotion, "dcm"), get(reference_locomotion, "dcm")
+        io.position, io.position_reference = get(actuation, "position"), get(trajectory, "position")
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.value, io.reference, io.rewards = ptr(self.value), ptr(self.reference), ptr(self.rewards)
+        self._check(self._L.jm_block_tracking_rewards(self._plan, self._dtype, eng.batch_size, self._C.byref(io), self._cutoff,
+                                                      eng._stream()))
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The rewards at the state of a new episode on the masked lanes (every lane without a mask); the other lanes keep
+        every tensor bit for bit.  Call it after the reset of every block it reads."""
+        eng = self._eng
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        self._launch(mask)
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream, behind the refresh of every block it reads."""
+        self._launch(None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_trackrewards_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
 
 
 def pd_controller(encoder_data: torch.Tensor, command_state: torch.Tensor,

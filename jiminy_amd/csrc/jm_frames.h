@@ -45,24 +45,26 @@ constexpr int MODEL_LANE_ROWS = 13, MODEL_LANE_PLACEMENT = 10;  // (JM_F_MODEL_L
 inline int frames_nq_of(int kind) { return kind == SEG_NONE ? 0 : kind == SEG_UNBOUNDED ? 2 : kind == SEG_QUAT ? 4 : kind == FR_FREEFLYER ? 7 : 1; }
 inline int frames_nv_of(int kind) { return kind == SEG_NONE ? 0 : kind == SEG_QUAT ? 3 : kind == FR_FREEFLYER ? 6 : 1; }
 
-// Validate a description and pack it.  Returns false and a message on a malformed description.
-inline bool frames_pack(const jm_frames_desc * d, std::vector<int32_t> & it, std::vector<double> & dt, std::string & why)
+// Validate a description of walks and pack it.  Returns false and a message on a malformed description.  `caller`, `noun`:
+// the entry point and the name of a walk in the messages (jm_centroidal.h packs its bodies through here).
+inline bool walks_pack(const jm_frames_desc * d, std::vector<int32_t> & it, std::vector<double> & dt, std::string & why,
+                       const char * caller, const char * noun)
 {
-    const std::string who = "jm_frames_plan_create: ";
+    const std::string who = std::string(caller) + ": ", frame = std::string(noun) + " ";
     if (!d) { why = who + "null description"; return false; }
     if (!d->frame_seg_start || !d->frame_mode || !d->seg_kind || !d->seg_joint || !d->seg_q_index || !d->seg_v_index ||
         !d->seg_rot || !d->seg_trans || !d->seg_axis)
     { why = who + "null array in the description"; return false; }
     if (d->n_frames <= 0 || d->n_seg <= 0 || d->nq < 0 || d->nv < 0 || d->njoints <= 0) { why = who + "bad sizes"; return false; }
     if (d->frame_seg_start[0] != 0 || d->frame_seg_start[d->n_frames] != d->n_seg)
-    { why = who + "frame_seg_start must run from 0 to n_seg"; return false; }
+    { why = who + noun + "_seg_start must run from 0 to n_seg"; return false; }
     for (int f = 0; f < d->n_frames; ++f)
     {
         const int n = d->frame_seg_start[f + 1] - d->frame_seg_start[f];
         if (n <= 0 || n > FR_MAX_SEGS_PER_FRAME)
-        { why = who + "frame " + std::to_string(f) + " has a bad segment count (1 .. " + std::to_string(FR_MAX_SEGS_PER_FRAME) + ")"; return false; }
+        { why = who + frame + std::to_string(f) + " has a bad segment count (1 .. " + std::to_string(FR_MAX_SEGS_PER_FRAME) + ")"; return false; }
         if (d->frame_mode[f] < FR_LOCAL || d->frame_mode[f] > FR_ODOMETRY)
-        { why = who + "frame " + std::to_string(f) + " has an unknown reference frame mode"; return false; }
+        { why = who + frame + std::to_string(f) + " has an unknown reference frame mode"; return false; }
     }
     for (int s = 0; s < d->n_seg; ++s)
     {
@@ -107,6 +109,130 @@ inline bool frames_pack(const jm_frames_desc * d, std::vector<int32_t> & it, std
     return true;
 }
 
+// Validate the description of the frame kinematics and pack it.
+inline bool frames_pack(const jm_frames_desc * d, std::vector<int32_t> & it, std::vector<double> & dt, std::string & why)
+{
+    return walks_pack(d, it, dt, why, "jm_frames_plan_create", "frame");
+}
+
+// The state of a walk: world rotation and position, angular velocity and velocity of the origin in the world frame, and --
+// for the walks that carry accelerations (jm_centroidal.h) -- the time derivatives of the two velocities.
+template<class T> struct FrameWalk
+{
+    M3<T> R;
+    V3<T> p, w, pd, wd, pdd;
+};
+template<class T> JM_DEV FrameWalk<T> frame_walk_start()
+{
+    return {ident3<T>(), zero3<T>(), zero3<T>(), zero3<T>(), zero3<T>(), zero3<T>()};
+}
+
+// One segment of a walk: the constant placement `d` (FR_SEG_DOUBLES), then the motion of the joint `is` (FR_SEG_INTS) names.
+// `first`: the first segment of the walk (its rotation is the placement's).  `moving`: `w`, `pd` follow from `v`.  ACC (with
+// `moving`): `wd`, `pdd` follow as well; `acc` `[nv][B]` holds the joint accelerations in pinocchio's convention (the time
+// derivative of the rows of `v`), null: zeros, which leaves the velocity-product terms.
+template<class T, bool ACC>
+JM_DEV void frame_walk_segment(FrameWalk<T> & k, bool first, const double * __restrict__ d, const int * __restrict__ is,
+                               const T * __restrict__ q, const T * __restrict__ v, const T * __restrict__ acc,
+                               const T * __restrict__ model_lane, bool moving, long long B, long long lane)
+{
+    const int kind = is[0];
+    V3<T> t = v3((T)d[9], (T)d[10], (T)d[11]);
+    if (model_lane && kind != SEG_NONE)
+    {
+        const T * ml = model_lane + ((long long)is[1] * MODEL_LANE_ROWS + MODEL_LANE_PLACEMENT) * B + lane;
+        t = v3(ml[0], ml[B], ml[2 * B]);
+    }
+    const V3<T> off = k.R * t;
+    k.p = k.p + off;
+    if (moving)
+    {
+        const V3<T> wo = cross(k.w, off);
+        if (ACC) k.pdd = k.pdd + cross(k.wd, off) + cross(k.w, wo);
+        k.pd = k.pd + wo;
+    }
+    const M3<T> Cm = {(T)d[0], (T)d[1], (T)d[2], (T)d[3], (T)d[4], (T)d[5], (T)d[6], (T)d[7], (T)d[8]};
+    k.R = first ? Cm : k.R * Cm;
+    if (kind == SEG_NONE) return;
+    const T * qr = q + (long long)is[2] * B + lane;
+    const T * vr = moving ? v + (long long)is[3] * B + lane : nullptr;
+    const T * ar = ACC && moving && acc ? acc + (long long)is[3] * B + lane : nullptr;
+    if (kind == SEG_QUAT || kind == FR_FREEFLYER)
+    {
+        // the velocity rows of both are expressed in the frame behind the joint (free-flyer: linear, then angular)
+        if (kind == FR_FREEFLYER)
+        {
+            const V3<T> o2 = k.R * v3(qr[0], qr[B], qr[2 * B]);
+            k.p = k.p + o2;
+            if (moving)
+            {
+                const V3<T> wo = cross(k.w, o2);
+                if (ACC) k.pdd = k.pdd + cross(k.wd, o2) + cross(k.w, wo);
+                k.pd = k.pd + wo;
+            }
+            qr += 3 * B;
+        }
+        k.R = k.R * quat_to_matrix<T>(qr[0], qr[B], qr[2 * B], qr[3 * B]);
+        if (moving)
+        {
+            V3<T> vl = zero3<T>();
+            if (kind == FR_FREEFLYER)
+            {
+                vl = k.R * v3(vr[0], vr[B], vr[2 * B]);
+                k.pd = k.pd + vl;
+                vr += 3 * B;
+            }
+            const V3<T> wj = k.R * v3(vr[0], vr[B], vr[2 * B]);
+            if (ACC)
+            {
+                // (the offset of a free-flyer turns with the frame in front of it, its velocity rows with the one behind)
+                if (kind == FR_FREEFLYER)
+                {
+                    k.pdd = k.pdd + cross(k.w, vl) + cross(k.w + wj, vl);
+                    if (ar) { k.pdd = k.pdd + k.R * v3(ar[0], ar[B], ar[2 * B]); ar += 3 * B; }
+                }
+                k.wd = k.wd + cross(k.w, wj);
+                if (ar) k.wd = k.wd + k.R * v3(ar[0], ar[B], ar[2 * B]);
+            }
+            k.w = k.w + wj;
+        }
+        return;
+    }
+    const bool aligned = kind <= 3 || (kind >= FR_PX && kind < FR_PAXIS);
+    const int c = kind <= 3 ? kind - 1 : kind - FR_PX;
+    const V3<T> a = aligned ? v3(T(c == 0), T(c == 1), T(c == 2)) : v3((T)d[12], (T)d[13], (T)d[14]);
+    const V3<T> z = k.R * a;      // (the joint's own motion leaves its axis where it is)
+    if (kind >= FR_PX)
+    {
+        const V3<T> o2 = qr[0] * z;
+        k.p = k.p + o2;
+        if (moving)
+        {
+            const V3<T> wo = cross(k.w, o2);
+            if (ACC)
+            {
+                k.pdd = k.pdd + cross(k.wd, o2) + cross(k.w, wo) + (T(2) * vr[0]) * cross(k.w, z);
+                if (ar) k.pdd = k.pdd + ar[0] * z;
+            }
+            k.pd = k.pd + wo + vr[0] * z;
+        }
+        return;
+    }
+    T sn, cs;
+    if (kind == SEG_UNBOUNDED) { cs = qr[0]; sn = qr[B]; }
+    else sincos_(qr[0], &sn, &cs);
+    k.R = k.R * (kind <= 3 ? rot_axis<T>(c, cs, sn) : rot_rodrigues<T>(a, cs, sn));
+    if (moving)
+    {
+        if (ACC)
+        {
+            k.wd = k.wd + vr[0] * cross(k.w, z);
+            if (ar) k.wd = k.wd + ar[0] * z;
+        }
+        k.w = k.w + vr[0] * z;
+    }
+}
+
 // Pose and velocity of every frame of the plan for one lane.  q `[nq][B]`; v `[nv][B]` (read only when `vel` is given);
 // model_lane `[13 * njoints][B]` or null: the translation of every joint placement is then the lane's own
 // (rows 13 j + 10 .. 13 j + 12) instead of the plan's.  pose, pose_prev `[7][K][B]`; rpy `[3][K][B]`; vel `[6][K][B]`
@@ -122,67 +248,12 @@ JM_DEV void frame_kinematics_lane(const int32_t * __restrict__ it, const double 
     for (int f = 0; f < K; ++f)
     {
         const int s0 = it[2 + 3 * f], s1 = s0 + it[3 + 3 * f], mode = it[4 + 3 * f];
-        // world rotation and position of the walk, angular velocity and velocity of its origin in the world frame
-        M3<T> R = ident3<T>();
-        V3<T> p = zero3<T>(), w = zero3<T>(), pd = zero3<T>();
+        FrameWalk<T> k = frame_walk_start<T>();
         for (int s = s0; s < s1; ++s)
-        {
-            const double * d = dt + (long long)s * FR_SEG_DOUBLES;
-            const int * is = it + si + FR_SEG_INTS * s;
-            const int kind = is[0];
-            V3<T> t = v3((T)d[9], (T)d[10], (T)d[11]);
-            if (model_lane && kind != SEG_NONE)
-            {
-                const T * ml = model_lane + ((long long)is[1] * MODEL_LANE_ROWS + MODEL_LANE_PLACEMENT) * B + lane;
-                t = v3(ml[0], ml[B], ml[2 * B]);
-            }
-            const V3<T> off = R * t;
-            p = p + off;
-            if (moving) pd = pd + cross(w, off);
-            const M3<T> Cm = {(T)d[0], (T)d[1], (T)d[2], (T)d[3], (T)d[4], (T)d[5], (T)d[6], (T)d[7], (T)d[8]};
-            R = s == s0 ? Cm : R * Cm;
-            if (kind == SEG_NONE) continue;
-            const T * qr = q + (long long)is[2] * B + lane;
-            const T * vr = moving ? v + (long long)is[3] * B + lane : nullptr;
-            if (kind == SEG_QUAT || kind == FR_FREEFLYER)
-            {
-                // the velocity rows of both are expressed in the frame behind the joint (free-flyer: linear, then angular)
-                if (kind == FR_FREEFLYER)
-                {
-                    const V3<T> o2 = R * v3(qr[0], qr[B], qr[2 * B]);
-                    p = p + o2;
-                    if (moving) pd = pd + cross(w, o2);
-                    qr += 3 * B;
-                }
-                R = R * quat_to_matrix<T>(qr[0], qr[B], qr[2 * B], qr[3 * B]);
-                if (moving)
-                {
-                    if (kind == FR_FREEFLYER)
-                    {
-                        pd = pd + R * v3(vr[0], vr[B], vr[2 * B]);
-                        vr += 3 * B;
-                    }
-                    w = w + R * v3(vr[0], vr[B], vr[2 * B]);
-                }
-                continue;
-            }
-            const bool aligned = kind <= 3 || (kind >= FR_PX && kind < FR_PAXIS);
-            const int k = kind <= 3 ? kind - 1 : kind - FR_PX;
-            const V3<T> a = aligned ? v3(T(k == 0), T(k == 1), T(k == 2)) : v3((T)d[12], (T)d[13], (T)d[14]);
-            const V3<T> z = R * a;      // (the joint's own motion leaves its axis where it is)
-            if (kind >= FR_PX)
-            {
-                const V3<T> o2 = qr[0] * z;
-                p = p + o2;
-                if (moving) pd = pd + cross(w, o2) + vr[0] * z;
-                continue;
-            }
-            T sn, cs;
-            if (kind == SEG_UNBOUNDED) { cs = qr[0]; sn = qr[B]; }
-            else sincos_(qr[0], &sn, &cs);
-            R = R * (kind <= 3 ? rot_axis<T>(k, cs, sn) : rot_rodrigues<T>(a, cs, sn));
-            if (moving) w = w + vr[0] * z;
-        }
+            frame_walk_segment<T, false>(k, s == s0, dt + (long long)s * FR_SEG_DOUBLES, it + si + FR_SEG_INTS * s, q, v, nullptr,
+                                         model_lane, moving, B, lane);
+        const M3<T> & R = k.R;
+        const V3<T> & p = k.p, & w = k.w, & pd = k.pd;
         const long long o = (long long)f * B + lane;
         const Quat<T> e = matrix_to_quat(R);
         if (pose)

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows and of the reference trajectories, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state and of the tracking rewards, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -21,6 +21,8 @@
 #include "jm_footposes.h"
 #include "jm_tracking.h"
 #include "jm_trajectory.h"
+#include "jm_centroidal.h"
+#include "jm_trackrewards.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -126,6 +128,18 @@ struct jm_trajectory_plan
     {
         if (data) (void)hipFree(data);
     }
+};
+
+// the centroidal quantities of a state (jm_centroidal.h)
+struct jm_centroidal_plan
+{
+    DevicePlan dev;
+};
+
+// the tracking rewards (jm_trackrewards.h)
+struct jm_trackrewards_plan
+{
+    DevicePlan dev;
 };
 
 extern "C"
@@ -505,6 +519,62 @@ int32_t jm_block_trajectory_state(const jm_trajectory_plan * p, int32_t dtype, i
         const jm::TrajIO<T> a{io->time, io->trajectory, io->time_offset, io->lane_mask, (T *)io->q, (T *)io->v, (T *)io->a,
                               (T *)io->command, (T *)io->odom_pose, (T *)io->position, io->status};
         hipLaunchKernelGGL((jm::k_trajectory_state<T>), grid, dim3(256), 0, s, it, dt, (const T *)data, a, (long long)B);
+    });
+}
+
+int32_t jm_centroidal_plan_create(const jm_centroidal_desc * desc, jm_centroidal_plan ** out)
+{
+    return plan_create("jm_centroidal_plan_create", desc, out, jm::centroidal_pack);
+}
+
+int32_t jm_centroidal_plan_destroy(jm_centroidal_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_centroidal_state(const jm_centroidal_plan * p, int32_t dtype, int64_t B, const void * q, const void * v,
+                                  const void * a, const uint8_t * lane_mask, void * centroidal, void * stream)
+{
+    if (!p || !q || !v) return fail(JM_EINVAL, "jm_block_centroidal_state: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_centroidal_state: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_centroidal_state: bad dtype");
+    if (!centroidal) return JM_OK;      // (the only output is absent: nothing is written)
+    const jm::FramesArgs args{p->dev.it, p->dev.dt};
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((jm::k_centroidal_state<T>), grid, dim3(256), 0, s, args, (const T *)q, (const T *)v, (const T *)a,
+                           lane_mask, (T *)centroidal, (long long)B);
+    });
+}
+
+int32_t jm_trackrewards_plan_create(const jm_trackrewards_desc * desc, jm_trackrewards_plan ** out)
+{
+    return plan_create("jm_trackrewards_plan_create", desc, out, jm::trackrewards_pack);
+}
+
+int32_t jm_trackrewards_plan_destroy(jm_trackrewards_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_tracking_rewards(const jm_trackrewards_plan * p, int32_t dtype, int64_t B, const jm_trackrewards_io * io,
+                                  const double * cutoff, void * stream)
+{
+    if (!p || !io || !cutoff) return fail(JM_EINVAL, "jm_block_tracking_rewards: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_tracking_rewards: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_tracking_rewards: bad dtype");
+    jm::TrkRewCutoffs c;
+    for (int k = 0; k < jm::TR_TERMS; ++k) c.c[k] = cutoff[k] > 0.0 ? cutoff[k] : 0.0;     // (NaN: skipped as well)
+    const int32_t * it = p->dev.it;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::TrkRewIO<T> a{(const T *)io->pose, (const T *)io->pose_reference, (const T *)io->v_avg, (const T *)io->quat_no_yaw,
+                                (const T *)io->v_avg_reference, (const T *)io->quat_no_yaw_reference, (const T *)io->dcm,
+                                (const T *)io->dcm_reference, (const T *)io->position, (const T *)io->position_reference, io->lane_mask,
+                                (T *)io->value, (T *)io->reference, (T *)io->rewards};
+        hipLaunchKernelGGL((jm::k_tracking_rewards<T>), grid, dim3(256), 0, s, it, a, c, (long long)B);
     });
 }
 

@@ -431,7 +431,8 @@ class WalkerVecEnv(VecJiminyEnv):
                  frame_kinematics: Optional[Dict[str, Any]] = None, terminations: Optional[Dict[str, Any]] = None,
                  locomotion_quantities: Optional[Dict[str, Any]] = None, actuated_joints: Optional[Dict[str, Any]] = None,
                  foot_poses: Optional[Dict[str, Any]] = None, trajectory_tracking: Optional[Dict[str, Any]] = None,
-                 trajectory_database: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
+                 trajectory_database: Optional[Dict[str, Any]] = None, tracking_rewards: Optional[Dict[str, Any]] = None,
+                 **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -484,8 +485,21 @@ class WalkerVecEnv(VecJiminyEnv):
         # trajectory's state (on the nominal model) into `foot_poses.reference_relative_pose`.  A lane whose query time leaves a
         # trajectory of mode "raise" is truncated.  `_update_tracking_reference` is still called where it was: a subclass can
         # overwrite what the database wrote.
+        # optional `blocks.TrackingRewards`: `tracking_rewards={"base_height_cutoff": ..., "odometry_velocity_cutoff": ...,
+        # "capture_point_cutoff": ..., "joint_positions_cutoff": ...}` (each or None), exposed as `tracking_rewards`; needs
+        # `trajectory_database`.  With it the reference side is evaluated on the trajectory's state, on the nominal model: one
+        # frame kinematics block over the root joint, the contact frames and (with `foot_poses`) the feet where a term reads
+        # one, and for the capture point a `blocks.CentroidalState` and a `blocks.LocomotionQuantities(state=...)`, refreshed
+        # behind every query.  What reads it:
+        #   reward_mixture['base_height'] / ['odometry_velocity'] / ['capture_point'] / ['joint_positions']
+        #                                              ≙ `TrackingBaseHeightReward`, `TrackingBaseOdometryVelocityReward`,
+        #                                              `TrackingCapturePointReward` (compositions/locomotion.py:33-143),
+        #                                              `TrackingActuatedJointPositionsReward` (compositions/generic.py:125-150),
+        #                                              weights on the reward rows of the block
+        #   reward_mixture['foot_force_distribution'] is refused: a recorded trajectory carries no constraint multipliers.
         self.frames = self.locomotion = self.actuation = self.foot_poses = self.tracking = None
         self.trajectory = self._reference_frames = self._reference_foot_poses = None
+        self.tracking_rewards = self._reference_centroidal = self._reference_locomotion = None
         self._terminations = dict(terminations or {})
         tracking_terms = {"drift_odom_position": "odometry_horizon", "drift_odom_orientation": "odometry_horizon",
                           "shift_foot_positions": "foot_horizon", "shift_foot_orientations": "foot_horizon",
@@ -550,6 +564,44 @@ class WalkerVecEnv(VecJiminyEnv):
                     raise ValueError(f"trajectory_tracking['{horizon}'] reads the block of {keyword}: give {keyword} as well")
         elif "odom_pose" in self.reward_mixture:
             raise ValueError("the odom_pose reward term reads the tracking windows block: give trajectory_tracking as well")
+        if "foot_force_distribution" in self.reward_mixture:
+            raise NotImplementedError("reward_mixture['foot_force_distribution'] (`TrackingFootForceDistributionReward`): a "
+                                      "recorded trajectory carries no constraint multipliers (`State.lambda_c`)")
+        reward_terms = ("base_height", "odometry_velocity", "capture_point", "joint_positions")
+        if tracking_rewards is not None:
+            tracking_rewards = dict(tracking_rewards)
+            unknown = set(tracking_rewards) - {f"{term}_cutoff" for term in reward_terms}
+            if unknown:
+                raise ValueError(f"unknown keys in tracking_rewards: {sorted(unknown)} "
+                                 f"({', '.join(f'{term}_cutoff' for term in reward_terms)})")
+            for term in reward_terms:
+                if term in self.reward_mixture and tracking_rewards.get(f"{term}_cutoff") is None:
+                    raise ValueError(f"reward_mixture['{term}'] needs tracking_rewards['{term}_cutoff']")
+            if trajectory_database is None or "dataset" not in trajectory_database:
+                raise ValueError("tracking_rewards compares with a reference trajectory: give trajectory_database as well")
+            on = {term for term in reward_terms if tracking_rewards.get(f"{term}_cutoff") is not None}
+            if {"odometry_velocity", "capture_point"} & on and any(
+                    getattr(pair[0], "v", None) is None for pair in trajectory_database["dataset"].values() if isinstance(pair, tuple)):
+                raise ValueError("tracking_rewards['odometry_velocity_cutoff'] and ['capture_point_cutoff'] need a dataset with v")
+            if "joint_positions" in on and actuated_joints is None:
+                raise ValueError("tracking_rewards['joint_positions_cutoff'] reads the actuated-joint quantities block: give "
+                                 "actuated_joints as well")
+            if "capture_point" in on:
+                if locomotion_quantities is None:
+                    raise ValueError("tracking_rewards['capture_point_cutoff'] reads the locomotion quantities block: give "
+                                     "locomotion_quantities as well")
+                if locomotion_quantities.get("dcm_reference_frame", "LOCAL") not in ("LOCAL", 0):
+                    raise ValueError("tracking_rewards['capture_point_cutoff'] tracks the capture point in the odometry frame: "
+                                     "locomotion_quantities['dcm_reference_frame'] must be 'LOCAL'")
+            if {"base_height", "odometry_velocity"} & on:
+                # (the true side reads the root joint and the contact frames, the velocity their step average)
+                frame_kinematics = dict(frame_kinematics or {})
+                if "odometry_velocity" in on:
+                    frame_kinematics["average"] = True
+            self._tracking_rewards_on = on
+        elif set(reward_terms) & set(self.reward_mixture):
+            raise ValueError("the base_height, odometry_velocity, capture_point and joint_positions reward terms read the "
+                             "tracking rewards block: give tracking_rewards as well")
         no_frames = {"mechanical_safety", "power_consumption", *tracking_terms}
         if set(self._terminations) - no_frames and frame_kinematics is None:
             raise ValueError("the terminations read the frame kinematics block: give frame_kinematics as well")
@@ -559,6 +611,12 @@ class WalkerVecEnv(VecJiminyEnv):
                 names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities)
             else:
                 names, modes, cfg = self.frame_kinematics_config(self.model, frame_kinematics, reading, locomotion_quantities, foot_poses)
+            if tracking_rewards is not None and {"base_height", "odometry_velocity"} & self._tracking_rewards_on:
+                for name in ["root_joint"] + list(self.model.contacts):
+                    if name not in names:
+                        names.append(name)
+                        if modes is not None:
+                            modes.append("LOCAL")
             self.frames = blocks.FrameKinematics(self.engine, names, reference_frames=modes, **cfg)
             if foot_poses is not None:
                 self.foot_poses = blocks.FootPoseQuantities(self.engine, self.frames, **foot_poses)
@@ -593,13 +651,41 @@ class WalkerVecEnv(VecJiminyEnv):
                 self.trajectory.bind_references(self.tracking)
             self._trajectory_time = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
             self._trajectory_time_own = None if self.dtype == torch.float64 else torch.zeros_like(self._t0)
-            if self.foot_poses is not None:
-                feet = list(self.foot_poses.foot_frame_names)
+            feet = [] if self.foot_poses is None else list(self.foot_poses.foot_frame_names)
+            on = self._tracking_rewards_on if tracking_rewards is not None else set()
+            if {"base_height", "odometry_velocity", "capture_point"} & on:
+                # the reference side: ONE frame kinematics block over the root joint, the contact frames and the feet, and
+                # for the capture point the centroidal rows and the locomotion quantities of the trajectory's state; each
+                # block exists only where a term reads it
+                names = ["root_joint"] + list(self.model.contacts)
+                names += [name for name in feet if name not in names]
+                self._reference_frames = blocks.FrameKinematics(self.engine, names, compute_velocity=False,
+                                                                average="odometry_velocity" in on,
+                                                                state=(self.trajectory.q, self.trajectory.v))
+                if "capture_point" in on:
+                    traj = self.trajectory
+                    self._reference_centroidal = blocks.CentroidalState(self.engine, state=(traj.q, traj.v, traj.a))
+                    cfg = {k: locomotion_quantities[k] for k in ("foot_frame_names", "zmp_reference_frame", "dcm_reference_frame")
+                           if k in locomotion_quantities}
+                    self._reference_locomotion = blocks.LocomotionQuantities(
+                        self.engine, self._reference_frames, state=(traj.q, self._reference_centroidal), forces=False,
+                        momentum=False, **cfg)
+            elif self.foot_poses is not None:
                 self._reference_frames = blocks.FrameKinematics(self.engine, feet, compute_velocity=False,
                                                                 state=(self.trajectory.q, self.trajectory.v))
+            if self.foot_poses is not None:
                 self._reference_foot_poses = blocks.FootPoseQuantities(self.engine, self._reference_frames, foot_frame_names=feet)
                 # (its relative poses ARE the reference of the true side: no copy)
                 self._reference_foot_poses.relative_pose = self.foot_poses.reference_relative_pose
+            if tracking_rewards is not None:
+                reads_frames = bool({"base_height", "odometry_velocity"} & on)
+                self.tracking_rewards = blocks.TrackingRewards(
+                    self.engine, frames=self.frames if reads_frames else None,
+                    reference_frames=self._reference_frames if reads_frames else None,
+                    locomotion=self.locomotion if "capture_point" in on else None,
+                    reference_locomotion=self._reference_locomotion if "capture_point" in on else None,
+                    actuation=self.actuation if "joint_positions" in on else None,
+                    trajectory=self.trajectory if "joint_positions" in on else None, **tracking_rewards)
         m = self.model
         lim = torch.tensor([mo.effort_limit * mo.velocity_limit for mo in m.motors], dtype=self.dtype)
         self._power_consumption_max = float(lim.sum())  # locomotion.py:230-236
@@ -668,8 +754,10 @@ class WalkerVecEnv(VecJiminyEnv):
             raise RuntimeError("select_trajectory needs trajectory_database")
         self.trajectory.select(name_or_indices, lane_mask, time_offset_ratio)
 
-    def _query_trajectory(self, lane_mask: Optional[torch.Tensor]) -> None:
-        """The reference state of the (masked) lanes at their episode time, and what the reference-side blocks make of it."""
+    def _query_trajectory(self, lane_mask: Optional[torch.Tensor], step: bool = False) -> None:
+        """The reference state of the (masked) lanes at their episode time, and what the reference-side blocks make of it.
+        `step`: the query behind an environment step, which the step average of the reference frames advances over; any other
+        query restarts it."""
         if self._trajectory_time_own is None:
             torch.sub(self._clock, self._t0, out=self._trajectory_time)
         else:
@@ -677,12 +765,24 @@ class WalkerVecEnv(VecJiminyEnv):
             self._trajectory_time.copy_(self._trajectory_time_own)
         self.trajectory.query(self._trajectory_time, lane_mask)
         if self._reference_frames is not None:
-            if lane_mask is None:
+            averaged = self._reference_frames.average
+            if lane_mask is None and (step or not averaged):
                 self._reference_frames.refresh()
-                self._reference_foot_poses.refresh()
+                if averaged:
+                    self._reference_frames.refresh_average(self.step_dt)
             else:
                 self._reference_frames.reset(lane_mask)
-                self._reference_foot_poses.reset(lane_mask)
+            if self._reference_foot_poses is not None:
+                if lane_mask is None:
+                    self._reference_foot_poses.refresh()
+                else:
+                    self._reference_foot_poses.reset(lane_mask)
+        if self._reference_centroidal is not None:
+            for blk in (self._reference_centroidal, self._reference_locomotion):
+                if lane_mask is None:
+                    blk.refresh()
+                else:
+                    blk.reset(lane_mask)
 
     def reset(self, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
         out = super().reset(seed, options)
@@ -700,6 +800,8 @@ class WalkerVecEnv(VecJiminyEnv):
         if self.tracking is not None:
             self._update_tracking_reference(None)
             self.tracking.reset(None)
+        if self.tracking_rewards is not None:
+            self.tracking_rewards.reset(None)
         return out
 
     def reset_lanes(self, lane_mask: torch.Tensor) -> None:
@@ -718,6 +820,8 @@ class WalkerVecEnv(VecJiminyEnv):
         if self.tracking is not None:
             self._update_tracking_reference(lane_mask)
             self.tracking.reset(lane_mask)
+        if self.tracking_rewards is not None:
+            self.tracking_rewards.reset(lane_mask)
 
     def _after_step(self):
         self._dir_sum += self.engine.robot_state.q[1].to(torch.float64)
@@ -729,7 +833,7 @@ class WalkerVecEnv(VecJiminyEnv):
         if self.locomotion is not None:
             self.locomotion.refresh()
         if self.trajectory is not None:
-            self._query_trajectory(None)
+            self._query_trajectory(None, step=True)
         if self.foot_poses is not None:
             self.foot_poses.refresh()
         if self.actuation is not None:
@@ -737,6 +841,8 @@ class WalkerVecEnv(VecJiminyEnv):
         if self.tracking is not None:
             self._update_tracking_reference(None)
             self.tracking.refresh()
+        if self.tracking_rewards is not None:
+            self.tracking_rewards.refresh()
         return super()._after_step()
 
     def base_relative_height(self) -> torch.Tensor:
@@ -816,6 +922,9 @@ class WalkerVecEnv(VecJiminyEnv):
             total += self.reward_mixture["foot_orientations"] * self.foot_poses.reward_foot_orientations
         if "odom_pose" in self.reward_mixture:
             total += self.reward_mixture["odom_pose"] * self.tracking.reward_odom_pose
+        for term in ("base_height", "odometry_velocity", "capture_point", "joint_positions"):
+            if term in self.reward_mixture:
+                total += self.reward_mixture[term] * self.tracking_rewards.reward(term)
         return total
 
 

@@ -64,6 +64,24 @@ def make_desc(*, nq: int, nv: int, njoints: int, frame_seg_start, frame_mode, se
     return d, keep
 
 
+def joint_segment(model: CompiledModel, j: int):
+    """(kind, first q row, first v row, axis) of joint j as a segment of a walk (`PlacedSegmentTable.add_placed_frame`)."""
+    t, iq, iv = int(model.jtypes[j]), int(model.idx_q[j]), int(model.idx_v[j])
+    if t in AXIS_KIND:
+        return AXIS_KIND[t], iq, iv, model.axes[j]
+    if t in (JT_RUBX, JT_RUBY, JT_RUBZ, JT_RUBU):
+        return SEG_UNBOUNDED, iq, iv, model.axes[j] if t == JT_RUBU else np.eye(3)[t - JT_RUBX]
+    if t in (JT_PX, JT_PY, JT_PZ):
+        return SEG_PX + (t - JT_PX), iq, iv, np.eye(3)[t - JT_PX]
+    if t == JT_PU:
+        return SEG_PAXIS, iq, iv, model.axes[j]
+    if t == JT_SPHERICAL:
+        return SEG_QUAT, iq, iv, np.zeros(3)
+    if t == JT_FREEFLYER:
+        return SEG_FREEFLYER, iq, iv, np.zeros(3)
+    raise NotImplementedError(f"joint type {t} of joint '{model.joint_names[j]}'")
+
+
 def build_plan(model: CompiledModel, frame_names: Sequence[str],
                reference_frames: Optional[Sequence[Union[int, str]]] = None) -> FramePlan:
     """The plan of the frame kinematics for the named frames, in the given order.  `reference_frames`: one of LOCAL,
@@ -78,28 +96,12 @@ def build_plan(model: CompiledModel, frame_names: Sequence[str],
         raise ValueError(f"expected one reference frame per frame ({len(frame_names)}), got {len(modes)}")
     segs = PlacedSegmentTable()
 
-    def joint_segment(j: int):
-        t, iq, iv = int(model.jtypes[j]), int(model.idx_q[j]), int(model.idx_v[j])
-        if t in AXIS_KIND:
-            return AXIS_KIND[t], iq, iv, model.axes[j]
-        if t in (JT_RUBX, JT_RUBY, JT_RUBZ, JT_RUBU):
-            return SEG_UNBOUNDED, iq, iv, model.axes[j] if t == JT_RUBU else np.eye(3)[t - JT_RUBX]
-        if t in (JT_PX, JT_PY, JT_PZ):
-            return SEG_PX + (t - JT_PX), iq, iv, np.eye(3)[t - JT_PX]
-        if t == JT_PU:
-            return SEG_PAXIS, iq, iv, model.axes[j]
-        if t == JT_SPHERICAL:
-            return SEG_QUAT, iq, iv, np.zeros(3)
-        if t == JT_FREEFLYER:
-            return SEG_FREEFLYER, iq, iv, np.zeros(3)
-        raise NotImplementedError(f"joint type {t} of joint '{model.joint_names[j]}'")
-
     for name in frame_names:
         try:
             fr = model.frame(name)
         except LookupError:
             raise LookupError(f"frame '{name}' not found in model") from None
-        segs.add_placed_frame(model, int(fr.parent_joint), fr.R, fr.p, joint_segment)
+        segs.add_placed_frame(model, int(fr.parent_joint), fr.R, fr.p, lambda j: joint_segment(model, j))
     depth = list(np.diff(segs.frame_seg_start))
     if max(depth) > MAX_SEGS_PER_FRAME:
         raise NotImplementedError(f"a frame deeper than {MAX_SEGS_PER_FRAME} segments")
