@@ -193,6 +193,33 @@ static long long g_tip_solves = 0;   // solves that took the operational-space f
 extern "C" long long emu_tip_solves() { return g_tip_solves; }
 extern "C" void emu_set_split(int on) { g_split = on; }
 extern "C" int emu_has_split() { return jm::qcon_split<Topo>() ? 1 : 0; }
+// the topology's `jm::dispatch::Traits` as the library states them for float64 batches (jm_lib.cpp, traits_of):
+// quad, qcon_split, qcon_split_large, block_waves, lane_pgs
+// (`jm::quad_block_waves` sits in the device-only part of jm_quad.h: restated here over the same layout constants; the
+// test that reads these traits holds it to the block waves known for ANYmal and Atlas)
+template<class T, class Tp> static constexpr int emu_block_waves()
+{
+    constexpr long per_wave = (long)sizeof(T) * (jm::QRows<Tp>::NL * 64 + jm::QRows<Tp>::NB * 16);
+    constexpr long table = (long)sizeof(T) * jm::QLayout<Tp>::TABLE;
+    int best = 1, best_resident = 0;
+    for (int w = 1; w <= 4; w *= 2)
+    {
+        long blocks = (160L * 1024) / (table + w * per_wave);
+        if (blocks * w > 8) blocks = 8 / w;
+        const int resident = (int)blocks * w;
+        if (resident >= best_resident) { best = w; best_resident = resident; }
+    }
+    return best;
+}
+extern "C" void emu_dispatch_traits(int * out)
+{
+    if constexpr (Topo::QUAD)
+    {
+        out[0] = 1; out[1] = jm::qcon_split<Topo>(); out[2] = jm::qcon_split_large<Topo>();
+        out[3] = emu_block_waves<double, Topo>(); out[4] = jm::qcon_split_lane<Topo>();
+    }
+    else { out[0] = out[1] = out[2] = out[4] = 0; out[3] = 1; }
+}
 template<class T, class Tp> static void run_quad_con_split(const jm::BatchArgs<T> & A, const std::vector<T> & P, const jm::QConArgs<T> & C0)
 {
     if constexpr (jm::qcon_split<Tp>())

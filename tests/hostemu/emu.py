@@ -169,6 +169,14 @@ def lane_solves(model: CompiledModel) -> int:
     return int(_lib(model).emu_lane_solves())
 
 
+def dispatch_traits(model: CompiledModel) -> tuple:
+    """`jm::dispatch::Traits` of the topology for float64 batches, from the kernel headers themselves (jm_lib.cpp `traits_of`):
+    (quad, qcon_split, qcon_split_large, block_waves, lane_pgs) -- the tuples tests/test_dispatch_policy.py selects forms with."""
+    out = (C.c_int * 5)()
+    _lib(model).emu_dispatch_traits(out)
+    return tuple(int(x) for x in out)
+
+
 def tip_solves(model: CompiledModel) -> int:
     """Solves of the split form that took the operational-space form (jm_qtip.h) since the library was loaded."""
     return int(_lib(model).emu_tip_solves())

@@ -358,6 +358,17 @@ def mixed_grounded_and_free_batch(model, B: int, seed: int = 7):
 
 
 # ------------------------------------------------------------------ which form a launch takes (jm_dispatch.h on the host)
+# `jm::dispatch::Traits` of the robots of `tests.robots.quad_topology_models()`, in the form of tests/test_dispatch_policy.py
+# (quad, qcon_split, qcon_split_large, block_waves, lane_pgs).  Written out like ANYMAL / ATLAS there, so that a GPU test
+# compiles nothing; tests/test_model_compiler.py holds every tuple to what the kernel headers state (hostemu.dispatch_traits).
+QUAD_TOPOLOGY_TRAITS = {
+    "hydra": (1, 1, 1, 4, 0),           # 25 bounded joints + 4 x 6 contact rows = 49 > 32: large solves (split start / step)
+    "quadlet_bare": (1, 1, 0, 4, 1),    # 9 + 4 x 4 = 25 rows, 4 contact points: one lane per robot, history-driven
+    "quadlet_jside": (1, 1, 0, 4, 1),
+    "quadlet_free": (1, 0, 0, 4, 0),    # no contact point: 9 bound rows, never split
+}
+
+
 def expected_form(name: str, n_cus: int = 256, per_stage=None, **facts) -> str:
     """`select_form` (`select_adaptive_form` when `per_stage` is given) compiled for the host, as tests/test_dispatch_policy.py
     drives it, for the topology `name`."""
@@ -372,7 +383,7 @@ def expected_form(name: str, n_cus: int = 256, per_stage=None, **facts) -> str:
     out = os.path.join(codegen.BUILD, "libemu_dispatch.so")
     if (not os.path.exists(out)) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in (src, hdr)):
         subprocess.check_call(emu.host_compiler() + [src, "-o", out])
-    L, traits = C.CDLL(out), {"anymal": dp.ANYMAL, "atlas": dp.ATLAS}[name]
+    L, traits = C.CDLL(out), dict(QUAD_TOPOLOGY_TRAITS, anymal=dp.ANYMAL, atlas=dp.ATLAS)[name]
     if per_stage is not None:
         return dp.FORMS[L.dispatch_adaptive(*dp._args(traits, dict(facts, n_cus=n_cus)), int(per_stage))]
     return dp.select(L, traits, n_cus=n_cus, **facts)[0]

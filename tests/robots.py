@@ -70,6 +70,39 @@ def biped(torso: bool = False) -> CompiledModel:
                        has_freeflyer=True, name=name)
 
 
+def hydra() -> CompiledModel:
+    """Free-flying robot of 26 joints (the free-flyer and 25 motorised ones) whose trunk is a tree (codegen.quad_structure): waist, chest, a three-joint neck chain and a
+    tail of a revolute and an unaligned prismatic joint that branches off the waist's body next to the chest -- 8 trunk
+    joints (two `TrunkStore` slots per lane), two trunk children of one trunk joint, trunk parents that are neither the
+    root nor the joint before.  Two 5-joint legs on the base (toe + heel contact points) and two 4-joint arms on the chest
+    (one contact point each); IMUs on the base and the head, force sensors on the toes, motor-side encoders and effort
+    sensors everywhere, motors with effort and velocity limits and no friction."""
+    return build_robot(os.path.join(DATA, "hydra.urdf"), os.path.join(DATA, "hydra_hardware.toml"),
+                       has_freeflyer=True, name="hydra")
+
+
+QUADLET_VARIANTS = ("bare", "jside", "free")
+
+
+def quadlet(variant: str) -> CompiledModel:
+    """One small tree (an unaligned prismatic spine as the only trunk joint, four 2-joint legs) under three hardware files,
+    each a topology of the branch-parallel kernels of its own:
+    `bare`  -- one IMU and nothing else (no force / contact / encoder / effort sensors), motors without effort and without
+               velocity limit, one contact point per foot;
+    `jside` -- joint-side encoders (declared by `joint_name`), a contact sensor on every contact point, no effort and no
+               force sensors, motors with the effort limit and friction but without the velocity limit;
+    `free`  -- no contact points at all, motor-side encoders and effort sensors, motors with both limits."""
+    assert variant in QUADLET_VARIANTS
+    return build_robot(os.path.join(DATA, "quadlet.urdf"), os.path.join(DATA, f"quadlet_{variant}_hardware.toml"),
+                       has_freeflyer=True, name="quadlet_" + variant)
+
+
+def quad_topology_models() -> List[CompiledModel]:
+    """Robots that exist for compile-time branches of the branch-parallel kernels (tests/test_model_compiler.py lists them).
+    Not part of `all_test_models()`: that list parametrises the one-robot-per-lane tests."""
+    return [hydra()] + [quadlet(v) for v in QUADLET_VARIANTS]
+
+
 def hanging_pendulum() -> CompiledModel:
     """The reference's `simple_pendulum` fixture restated (tests/data/hanging_pendulum.urdf): bob welded 1 m below the
     pivot, motor without limits or armature (unit_py/utilities.py:18-59 `load_urdf_default`), IMU on the bob."""

@@ -41,7 +41,9 @@ TOL64 = 1e-11           # tests/test_gpu_parity.py: `centroidal` of the engine a
 POISON = 7.0
 B = 64
 MODELS = {"anymal": lambda: load_builtin("anymal"), "tree_arm_ff": lambda: robots.tree_arm(True),
-          "tree_arm_flex_ff": lambda: robots.tree_arm_flexible(True), "tree_arm": lambda: robots.tree_arm(False)}
+          "tree_arm_flex_ff": lambda: robots.tree_arm_flexible(True), "tree_arm": lambda: robots.tree_arm(False),
+          # 26 joints (free-flyer included) on a tree with two trunk branches (neck chain, tail) next to the limbs: against the numpy companion
+          "hydra": robots.hydra}
 ORACLE_MODELS = ("anymal", "tree_arm_ff", "tree_arm_flex_ff")
 _CACHE: dict = {}
 

@@ -20,6 +20,7 @@ from oracle.oracle_py import OracleEngine
 from tests import robots
 from tests.helpers import ReferenceFixedStepLoop, alloc_constraint_state, alloc_soa, oracle_batch, oracle_engine_step, rel_err
 from tests.hostemu import emu
+from tests.test_lane_failures import _CON, _Q, _assert_forms
 
 G = 9.81
 TIGHT = dict(tol_abs=1e-11, tol_rel=1e-10)  # PGS run to stagnation: iterates comparable to round-off
@@ -195,10 +196,44 @@ def _models():
         "crane_walker": robots.crane_walker,
         "biped": robots.biped,
         "biped_torso": lambda: robots.biped(True),
+        "hydra": robots.hydra,
+        # (the same robot; `_states` pushes a joint of either trunk branch past a bound, see `_trunk_bounds_states`)
+        TRUNK_BOUNDS: robots.hydra,
+        **{"quadlet_" + v: (lambda v=v: robots.quadlet(v)) for v in robots.QUADLET_VARIANTS},
     }
 
 
-def _states(model, B, seed):
+TRUNK_BOUNDS = "hydra+trunk_bounds"
+TRUNK_BRANCH_JOINTS = ("tail_a", "head_j")      # hydra: the tail and the neck chain leave the waist's body on two branches
+
+
+def _trunk_bounds_states(model, B, seed):
+    """Standing `hydra` with `tail_a` beyond a bound on every other lane and `head_j` on two lanes out of three (the recipe of
+    `_states` below, on these two trunk joints): a third of the lanes carry an active bound row on BOTH trunk branches.  The
+    columns of two such rows are the only input on which the ancestry test of the constraint rows (jm_qcon.h) answers "not an
+    ancestor" -- on a chain every earlier trunk joint is one."""
+    st = sample_standing_states(model, B, seed=seed, out_of_bounds_fraction=0.0)
+    rng = np.random.default_rng(seed)
+    lane = np.arange(B)
+    for jn, lanes in zip(TRUNK_BRANCH_JOINTS, (lane % 2 == 0, lane % 3 != 1)):
+        iq = int(model.idx_q[model.joint_index(jn)])
+        hi = rng.random(B) < 0.5
+        over = rng.uniform(-5e-4, 0.02, B)
+        st["q"][iq, lanes & hi] = model.position_upper[iq] + over[lanes & hi]
+        st["q"][iq, lanes & ~hi] = model.position_lower[iq] - over[lanes & ~hi]
+    return st
+
+
+def _assert_trunk_bounds_active(model, ref):
+    """From the oracle's flags: bound rows of both trunk branches active in the same lane, in at least a sixth of the lanes."""
+    rows = [model.bound_row(jn) for jn in TRUNK_BRANCH_JOINTS]
+    both = ((ref["con_flags"][rows[0]] & 1) != 0) & ((ref["con_flags"][rows[1]] & 1) != 0)
+    assert both.sum() >= max(1, ref["con_flags"].shape[1] // 6), both
+
+
+def _states(model, B, seed, name=None):
+    if name == TRUNK_BOUNDS:
+        return _trunk_bounds_states(model, B, seed)
     if model.has_freeflyer and model.ncontacts > 0:
         return sample_standing_states(model, B, seed=seed)
     st = sample_states(model, B, seed=seed)
@@ -215,8 +250,8 @@ def _states(model, B, seed):
     return st
 
 
-def _pair(model, B, seed):
-    st = _states(model, B, seed)
+def _pair(model, B, seed, name=None):
+    st = _states(model, B, seed, name)
     ref, got = alloc_soa(model, B), alloc_soa(model, B)
     for arr in (ref, got):
         alloc_constraint_state(model, arr, B)
@@ -235,11 +270,13 @@ def _check(got, ref, tol, what=""):
 
 
 # served by the branch-parallel kernel (jm_qcon.h); the bipeds with two / one empty limbs (codegen.quad_structure)
-QUAD_MODELS = ("anymal", "atlas", "crane_walker", "biped", "biped_torso")
+# ... and the robots of `robots.quad_topology_models()`, which the one-robot-per-lane cases leave out
+QUAD_ONLY = ("hydra", TRUNK_BOUNDS, "quadlet_bare", "quadlet_jside", "quadlet_free")
+QUAD_MODELS = ("anymal", "atlas", "crane_walker", "biped", "biped_torso") + QUAD_ONLY
 
 
-@pytest.mark.parametrize("name,variant", [(n, "lane") for n in _models()] + [(n, "quad") for n in QUAD_MODELS] +
-                         [("atlas", "split"), ("anymal", "split"), ("biped", "split")])
+@pytest.mark.parametrize("name,variant", [(n, "lane") for n in _models() if n not in QUAD_ONLY] + [(n, "quad") for n in QUAD_MODELS] +
+                         [("atlas", "split"), ("anymal", "split"), ("biped", "split"), ("hydra", "split"), (TRUNK_BOUNDS, "split")])
 def test_constraint_kernel_matches_oracle_on_the_host(name, variant):
     """Both device formulations compiled for the host against the oracle (the reference's dense one):
     `lane` = one robot per lane, sequential bias-free solves (jm_constraint.h); `quad` = four lanes per
@@ -250,9 +287,11 @@ def test_constraint_kernel_matches_oracle_on_the_host(name, variant):
     split = variant == "split"
     variant = "quad" if split else variant
     model = _models()[name]()
-    B = (3 if variant == "lane" else 6) if name == "atlas" else (8 if variant == "lane" else 12)   # (sized for the CPU suite)
-    ref, got = _pair(model, B, seed=7)
+    B = (3 if variant == "lane" else 6) if name in ("atlas", "hydra", TRUNK_BOUNDS) else (8 if variant == "lane" else 12)   # (sized for the CPU suite)
+    ref, got = _pair(model, B, seed=7, name=name)
     oracle_batch(model, ref, "start", constraint_options=TIGHT)
+    if name == TRUNK_BOUNDS:
+        _assert_trunk_bounds_active(model, ref)
     emu.run(model, got, "start", constraint_options=TIGHT, variant=variant, split=split)   # (split: the start passes as launches too)
     _check(got, ref, 1e-9, "start")
     n_active = int((ref["con_flags"] & 1).sum())
@@ -268,7 +307,7 @@ def test_constraint_kernel_matches_oracle_on_the_host(name, variant):
         # robots with few active joint rows solve in the operational space of their feet (jm_qtip.h), the others
         # stream the delassus matrix: this seeded batch exercises the first form
         assert emu.tip_solves(model) > 0
-    if split and name != "atlas":
+    if split and name in ("anymal", "biped"):
         # robots with few contact points: the solve of the split form runs one lane per robot (qcon_pgs_lane, round 6)
         assert emu.lane_solves(model) > lane_before
 
@@ -511,14 +550,18 @@ def test_spring_damper_path_is_untouched_by_the_constraint_state():
 # ------------------------------------------------------------------ device build (C ABI) vs oracle
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["anymal", "atlas", "crane_walker", "tree_arm", "point_mass", "biped", "biped_torso",
-                                  "tree_arm_flex", "tree_arm_flex_ff", "pendulum_backlash"])
+                                  "tree_arm_flex", "tree_arm_flex_ff", "pendulum_backlash",
+                                  "hydra", TRUNK_BOUNDS, "quadlet_bare", "quadlet_free"])
 def test_gpu_constraint_model_matches_oracle(name, gpu_device):
     import torch
 
     from jiminy_amd.engine import BatchedEngine
     model = _models()[name]()
-    B = 96 if name != "atlas" else 40
-    ref, _ = _pair(model, B, seed=11)
+    B = 96 if name not in ("atlas", "hydra", TRUNK_BOUNDS) else 40
+    ref, _ = _pair(model, B, seed=11, name=name)
+    if model.name == "hydra":
+        # (a batch that is no multiple of 16 stays on the single kernel, whatever the size of the solves)
+        _assert_forms(gpu_device, "hydra", B, [(dict(_Q, **_CON, mode="start"), "QCON_INIT"), (dict(_Q, **_CON, mode="step"), "QCON")])
     eng = BatchedEngine(model, B, dtype=torch.float64, device=gpu_device,
                         extra_outputs=("contact_forces", "f_external", "joint_forces", "energy", "centroidal"))
     dt = 5e-4
@@ -529,6 +572,8 @@ def test_gpu_constraint_model_matches_oracle(name, gpu_device):
         eng.set_command(torch.from_numpy(ref["command"]))
     eng.start(torch.from_numpy(ref["q"]), torch.from_numpy(ref["v"]))
     oracle_batch(model, ref, "start", constraint_options=TIGHT)
+    if name == TRUNK_BOUNDS:
+        _assert_trunk_bounds_active(model, ref)
     loop = ReferenceFixedStepLoop(dt)   # the reference's sub-step rule: opens with a 1 us step (engine.cc:1176)
 
     def check(tol, what, tol_forces=None):
@@ -642,12 +687,28 @@ def test_gpu_split_stepping_of_large_solves(gpu_device, monkeypatch, solver, n_s
     """Atlas-sized solves step through three launches per evaluation (k_quad_con_split<1> | k_qcon_pgs |
     k_quad_con_split<2>, jm_qcon.h) when the batch is a multiple of 16: same states, multipliers, flags and outputs
     as the single kernel (JIMINY_AMD_QCON_SPLIT=0) and as the oracle.  The large batch: compared with the single kernel."""
+    _split_stepping_of_large_solves(gpu_device, monkeypatch, "atlas", solver, n_sub, B)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,solver,n_sub,B", [("hydra", "runge_kutta_4", 1, 48), ("hydra", "euler_explicit", 2, 48),
+                                                 (TRUNK_BOUNDS, "runge_kutta_4", 1, 48)])
+def test_gpu_split_stepping_of_large_solves_on_a_trunk_tree(gpu_device, monkeypatch, name, solver, n_sub, B):
+    """The same on `hydra` (49 rows, a trunk tree of 8 joints: `trunk_column` with siblings, the ancestry test of two bound rows
+    on different trunk branches): SPLIT_START / SPLIT_STEP against the single kernel and the oracle, forms asserted from the policy."""
+    _split_stepping_of_large_solves(gpu_device, monkeypatch, name, solver, n_sub, B)
+
+
+def _split_stepping_of_large_solves(gpu_device, monkeypatch, name, solver, n_sub, B):
     import torch
 
     from jiminy_amd.engine import BatchedEngine
-    model = _models()["atlas"]()
+    model = _models()[name]()
     with_oracle = B <= 64
-    ref, _ = _pair(model, B, seed=23)
+    ref, _ = _pair(model, B, seed=23, name=name)
+    if model.name == "hydra":
+        _assert_forms(gpu_device, "hydra", B, [(dict(_Q, **_CON, mode="start"), "SPLIT_START"), (dict(_Q, **_CON, mode="step"), "SPLIT_STEP"),
+                                               (dict(_Q, **_CON, mode="step", split=0), "QCON")])
     dt = 2.5e-4
     engines = []
     for split in ("1", "0"):
@@ -663,6 +724,8 @@ def test_gpu_split_stepping_of_large_solves(gpu_device, monkeypatch, solver, n_s
     if with_oracle:
         oracle_batch(model, ref, "start", constraint_options=TIGHT)
         loop = ReferenceFixedStepLoop(dt)   # the reference's sub-step rule: opens with a 1 us step (engine.cc:1176)
+        if name == TRUNK_BOUNDS:
+            _assert_trunk_bounds_active(model, ref)
     for i in range(3):
         for eng in engines:
             eng.step(n_sub * dt)

@@ -205,12 +205,17 @@ def unbounded_model():
 
 
 MODELS = {"arm7": lambda: load_builtin("arm7"), "cartpole": lambda: load_builtin("cartpole"), "flex_arm": lambda: rd.flex_arm(False),
-          "unbounded": unbounded_model, "biped": robots.biped, "anymal": lambda: load_builtin("anymal")}
+          "unbounded": unbounded_model, "biped": robots.biped, "anymal": lambda: load_builtin("anymal"),
+          # a branched tree: the segment walk to the head and to the tail leaves the waist's body on different branches,
+          # the walk to a hand leaves the chest next to the neck
+          "hydra": robots.hydra}
 
 
 def model_frames(name: str, model) -> list:
     if name == "anymal":
         return ["root_joint"] + list(model.contacts) + [s["frame"] for s in model.sensors["ImuSensor"]]
+    if name == "hydra":
+        return ["head", "tail2", "l_palm", "r_toe"]
     return list(model.frames)[:12]
 
 
@@ -576,7 +581,7 @@ def device_case(name: str):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["arm7", "cartpole", "flex_arm", "anymal"])
+@pytest.mark.parametrize("name", ["arm7", "cartpole", "flex_arm", "anymal", "hydra"])
 def test_device_kinematics_match_the_numpy_forward_kinematics(name, gpu_device):
     """B = 300: two blocks, the second one partial; every frame of the case in one plan and its last frame alone."""
     lib = _prebuilt(load_builtin("cartpole"))

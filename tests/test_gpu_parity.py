@@ -406,12 +406,14 @@ def _teacher_forced_test(gpu_device, name, B, dt, steps, pool, min_contact_steps
     assert np.median(worst["a"]) <= 1e-9, np.median(worst["a"])
 
 
-@pytest.mark.parametrize("name", ["anymal", "atlas"])
+@pytest.mark.parametrize("name", ["anymal", "atlas", "hydra", "quadlet_bare"])
 def test_fp32_engines_of_the_branch_parallel_topologies(gpu_device, name):
     """float32 batches of the big robots (`bench.py --dtype f32`): the library self-test accepts the float32 kernels (its
     Runge-Kutta leg is conditioned for float64 only) and ten RK4 steps in free flight stay within float32 accuracy of the
-    float64 engine."""
-    model = load_builtin(name)
+    float64 engine.  `hydra` (trunk tree, two store slots per lane) and `quadlet_bare` (no sensor but an IMU, motors without
+    limits) are float32 instantiations of branches no other robot builds."""
+    from tests import robots
+    model = {"hydra": robots.hydra, "quadlet_bare": lambda: robots.quadlet("bare")}.get(name, lambda: load_builtin(name))()
     B, dt = 64, 2.5e-4
     st = sample_states(model, B, seed=3, base_height=(2.0, 2.5), grounded_fraction=0.0, command_fraction=0.3)
     out = {}
@@ -626,15 +628,21 @@ def test_adaptive_dopri_ragged_and_tiny_batches(gpu_device, B):
     assert abs(ss.t - 0.02) < 1e-12
 
 
-@pytest.mark.parametrize("name", ["crane_walker", "biped_torso"])
+@pytest.mark.parametrize("name", ["crane_walker", "biped_torso", "hydra"])
 def test_adaptive_dopri_crane_walker_trunk_tree_and_ragged_limbs(gpu_device, name):
     """The persistent stepper on the authored robot with a prismatic / unaligned trunk tree and limbs of 3/3/2/2 joints,
-    and on the biped with limbs of 3/3/1/0 joints: landings on the spring-damper ground, against the oracle."""
+    on the biped with limbs of 3/3/1/0 joints and on `hydra` (a trunk tree with two branches, limbs of 5/5/4/4): landings
+    on the spring-damper ground, against the oracle."""
     from tests import robots
-    model = robots.crane_walker() if name == "crane_walker" else robots.biped(True)
+    model = {"crane_walker": robots.crane_walker, "biped_torso": lambda: robots.biped(True), "hydra": robots.hydra}[name]()
     B = 48
-    st = sample_states(model, B, seed=19, base_height=(0.5, 0.8), grounded_fraction=0.4, command_fraction=0.2)
+    st = sample_states(model, B, seed=19, base_height=(0.9, 1.2) if name == "hydra" else (0.5, 0.8), grounded_fraction=0.4,
+                       command_fraction=0.2)
     eng, ref, ad = _dopri_pair(model, B, st, 5e-3, 6, 1e-7, 1e-8)
+    if name == "hydra":
+        from tests.test_lane_failures import _Q, _assert_forms
+        assert eng._adaptive_form() == 0        # (the persistent form, `k_quad_dopri`: what the policy then selects)
+        _assert_forms(gpu_device, "hydra", B, [(dict(_Q, per_stage=0), "DOPRI")])
     dev_status = eng.status.cpu().numpy().reshape(-1)
     ok = ((ref["status"][0] | dev_status) & 9) == 0
     assert ok.mean() > 0.9, (np.unique(ref["status"][0], return_counts=True), np.unique(dev_status, return_counts=True))

@@ -5,7 +5,8 @@ placement its own wind-up arrives at, and reads the status row back before its f
 wrong there depends on the robot (empty limbs, long limbs), on the launch mode and on which optional outputs are bound,
 so the cases below are
 
-  robots   anymal, biped (two leaf chains: empty limbs), atlas (long limbs, trunk tree)
+  robots   anymal, biped (two leaf chains: empty limbs), atlas (long limbs, trunk tree), hydra (trunk tree with two
+           branches), quadlet_jside (joint-side encoders, contact sensors, neither force nor effort sensors)
   batches  1 (partial quad wave), 17 (partial block), 80 (more than one block)
   modes    start | step, n_sub = 1 | step, n_sub = 3 | step after a command change | step without the sensor refresh |
            reset of every other lane | refresh
@@ -36,13 +37,17 @@ ROBOTS = {
     "anymal": (lambda: load_builtin("anymal"), dict(base_height=(0.3, 0.6), grounded_fraction=0.6), 5e-4),
     "biped": (robots.biped, dict(base_height=(0.55, 0.75), grounded_fraction=0.6), 2.5e-4),
     "atlas": (lambda: load_builtin("atlas"), dict(base_height=(0.85, 1.0), grounded_fraction=0.6), 2.5e-4),
+    # trunk tree with siblings and two store slots per lane (the pass walks the trunk bodies of every branch), IMU on the head
+    "hydra": (robots.hydra, dict(base_height=(0.9, 1.2), grounded_fraction=0.6), 2.5e-4),
+    # joint-side encoders, contact sensors, no force / effort sensors: sensor branches of the pass no other robot builds
+    "quadlet_jside": (lambda: robots.quadlet("jside"), dict(base_height=(0.25, 0.4), grounded_fraction=0.6), 2.5e-4),
 }
 BATCHES = (1, 17, 80)
 HOST_BATCHES = (1, 17)      # (waves and blocks are the device's: the host twins run one thread per lane whatever the batch)
 # (phase, what the launch is)
 PHASES = ("start", "step_1", "step_3", "step_changed", "step_no_sensors", "reset", "refresh")
-GPU_TOL = {"start": 1e-11, "steps": {"anymal": 1e-8, "atlas": 1e-8, "biped": 1e-9}, "reset": 1e-11}
-EMU_TOL = {"start": 2e-11, "steps": {"anymal": 1e-8, "atlas": 1e-8, "biped": 1e-8}, "reset": 5e-12}
+GPU_TOL = {"start": 1e-11, "steps": {"anymal": 1e-8, "atlas": 1e-8, "biped": 1e-9, "hydra": 1e-8, "quadlet_jside": 1e-9}, "reset": 1e-11}
+EMU_TOL = {"start": 2e-11, "steps": {"anymal": 1e-8, "atlas": 1e-8, "biped": 1e-8, "hydra": 1e-8, "quadlet_jside": 1e-8}, "reset": 5e-12}
 F32_TOL = {"q": 1e-4, "v": 5e-3, "rows": 5e-3}
 
 _MODELS, _STATES, _REFERENCE = {}, {}, {}

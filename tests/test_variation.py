@@ -54,11 +54,15 @@ def _model(name):
     if name == "biped_torso":
         from tests import robots
         return robots.biped(True)
+    # (`hydra`: the per-lane body parameters of the 7 movable trunk joints pass through `ma.rbi`, on both trunk branches)
+    if name == "hydra":
+        from tests import robots
+        return robots.hydra()
     return load_builtin(name)
 
 
 @pytest.mark.parametrize("name,constrained", [("anymal", False), ("anymal", True), ("atlas", False), ("atlas", True),
-                                              ("biped_torso", False), ("biped_torso", True)])
+                                              ("biped_torso", False), ("biped_torso", True), ("hydra", False), ("hydra", True)])
 def test_branch_parallel_code_with_variation_matches_oracle_on_the_host(name, constrained):
     model = _model(name)
     B = 16 if name == "anymal" else 4
@@ -389,7 +393,7 @@ def test_force_breakpoints_cut_the_launches():
 # ------------------------------------------------------------------ device build
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,constrained", [("anymal", False), ("anymal", True), ("atlas", False), ("atlas", True),
-                                              ("biped_torso", False), ("biped_torso", True)])
+                                              ("biped_torso", False), ("biped_torso", True), ("hydra", False), ("hydra", True)])
 def test_gpu_variation_matches_oracle(gpu_device, name, constrained):
     import torch
 
@@ -398,6 +402,11 @@ def test_gpu_variation_matches_oracle(gpu_device, name, constrained):
     B, dt = (96, 5e-4) if name == "anymal" else (24, 2.5e-4)
     st, ml, ground, applied = _scene(model, B, 9, constrained)
     copt = TIGHT if constrained else None
+    if name == "hydra":
+        from tests.test_lane_failures import _Q, _assert_forms
+        gen = dict(_Q, model_lane=1, ground=1, applied=1, constraint=int(constrained))
+        _assert_forms(gpu_device, "hydra", B, [(dict(gen, mode="start"), "QCON_GEN_INIT" if constrained else "QUAD_GEN"),
+                                               (dict(gen, mode="step"), "QCON_GEN" if constrained else "QUAD_GEN")])
     ref = alloc_soa(model, B)
     if constrained:
         alloc_constraint_state(model, ref, B)
