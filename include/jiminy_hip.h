@@ -768,6 +768,44 @@ int32_t jm_locomotion_plan_destroy(jm_locomotion_plan * plan);
 int32_t jm_block_locomotion(const jm_locomotion_plan * plan, int32_t dtype, int64_t batch_size, const jm_locomotion_io * io,
                             double momentum_cutoff, double friction_cutoff, void * stream);
 
+/* ---- Locomotion quantities on height-map ground: jm_block_locomotion with the ground of jm_batch_set_ground under the
+ * contact points, for the constraint contact model, whose contact rows live in the local frame [t0 t1 n] of the surface
+ * under each contact point (FrameConstraint::setNormal, core/src/constraints/frame_constraint.cc:62-68).  New symbols only:
+ * no existing structure or signature changed with them.
+ * jm_locomotion_ground: `heights` the device array `[ny][nx]` of the scalar type `dtype`, sample (iy, ix) at (x0 + ix dx,
+ *   y0 + iy dy), bilinear patches with flat continuation outside (the definition of jm_batch_set_ground); `offsets` `[2][B]`
+ *   or NULL: the lane's (x, y) offset of every query (JM_F_GROUND_OFFSET); `contact_ground` `[4][n_contacts][B]` or NULL, an
+ *   output: the height and the unit normal (x, y, z) of the ground under every contact point.
+ * jm_block_locomotion_ground: `ground` NULL or `heights` NULL is flat ground: the kernel of jm_block_locomotion is launched,
+ *   every output of `io` equals its bit for bit (`contact_ground`, where given, is then height 0 and normal e_z, written by a
+ *   second small launch).  Otherwise, for every contact point, the world position
+ *   of its frame (`io->pose`, required) plus the lane's offset is queried for the height h and the normal n, and
+ *     foot_force_vertical[n_feet]   `MultiFootNormalizedForceVertical` (quantities/locomotion.py:1272-1481): per contact
+ *                              t0_z lambda_x + t1_z lambda_y + n_z lambda_z, the third row of the constraint's `local_rotation`
+ *                              on its multipliers, summed per foot, over the weight
+ *     scalars[1]               ground_distance_min = min((z - h) n_z) (`_MultiContactMinGroundDistance`,
+ *                              compositions/locomotion.py:449-540)
+ *   Everything else is jm_block_locomotion's: `contact_force_rel`, scalars[0] and the friction reward stay in the local
+ *   contact frame, as in the reference; the ZMP, the DCM, the CoM and the momentum do not look at the ground.  Validated
+ *   before any device call (JM_EINVAL + jm_last_error): the arguments of jm_block_locomotion, nx < 2, ny < 2, a non-finite
+ *   x0 / y0, a non-positive or non-finite dx / dy, a height map without `io->pose`.  The launch allocates, copies and
+ *   synchronises nothing. */
+typedef struct jm_locomotion_ground
+{
+    const void * heights;
+    int32_t nx;
+    int32_t ny;
+    double x0;
+    double y0;
+    double dx;
+    double dy;
+    const void * offsets;
+    void * contact_ground;
+} jm_locomotion_ground;
+int32_t jm_block_locomotion_ground(const jm_locomotion_plan * plan, int32_t dtype, int64_t batch_size, const jm_locomotion_io * io,
+                                   const jm_locomotion_ground * ground, double momentum_cutoff, double friction_cutoff,
+                                   void * stream);
+
 /* ---- Actuated-joint quantities: kinematics of the actuated joints in motor order, distances to the mechanical stops, the
  * mechanical-safety count, the mechanical power, its sliding average over environment steps and the reward on it; batched,
  * one lane = one environment, one launch per refresh.  New symbols only: no existing structure or signature changed with

@@ -128,6 +128,13 @@ class LocomotionIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in LOCOMOTION_IO_FIELDS]
 
 
+class LocomotionGround(C.Structure):
+    """jm_locomotion_ground: the height map, the lanes' offsets and the `contact_ground` output of one launch of
+    jm_block_locomotion_ground (`heights` NULL: flat ground)."""
+    _fields_ = [("heights", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("x0", C.c_double), ("y0", C.c_double),
+                ("dx", C.c_double), ("dy", C.c_double), ("offsets", C.c_void_p), ("contact_ground", C.c_void_p)]
+
+
 class ActuationDesc(C.Structure):
     """jm_actuation_desc: the plan of the actuated-joint quantities (jiminy_amd.actuation builds it)."""
     _fields_ = [

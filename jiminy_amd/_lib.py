@@ -54,7 +54,7 @@ ABI_SYMBOLS = (
     "jm_attitude_plan_create", "jm_attitude_plan_destroy", "jm_block_attitude_init", "jm_block_mahony_observer",
     "jm_block_body_observer",
     "jm_frames_plan_create", "jm_frames_plan_destroy", "jm_block_frame_kinematics", "jm_block_frame_average",
-    "jm_locomotion_plan_create", "jm_locomotion_plan_destroy", "jm_block_locomotion",
+    "jm_locomotion_plan_create", "jm_locomotion_plan_destroy", "jm_block_locomotion", "jm_block_locomotion_ground",
     "jm_actuation_plan_create", "jm_actuation_plan_destroy", "jm_block_actuation",
     "jm_footposes_plan_create", "jm_footposes_plan_destroy", "jm_block_foot_poses",
     "jm_tracking_plan_create", "jm_tracking_plan_destroy", "jm_block_tracking",
@@ -129,6 +129,8 @@ class HipLibrary:
         L.jm_locomotion_plan_create.argtypes = [C.POINTER(_abi.LocomotionDesc), C.POINTER(vp)]
         L.jm_locomotion_plan_destroy.argtypes = [vp]
         L.jm_block_locomotion.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.LocomotionIO), C.c_double, C.c_double, vp]
+        L.jm_block_locomotion_ground.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.LocomotionIO),
+                                                 C.POINTER(_abi.LocomotionGround), C.c_double, C.c_double, vp]
         L.jm_actuation_plan_create.argtypes = [C.POINTER(_abi.ActuationDesc), C.POINTER(vp)]
         L.jm_actuation_plan_destroy.argtypes = [vp]
         L.jm_block_actuation.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.ActuationIO), C.c_int32, C.c_int32, C.c_double,

@@ -627,7 +627,7 @@ class CentroidalState:
 LOCOMOTION_SCALARS = ("force_vertical_max", "ground_distance_min", "reward_momentum", "reward_friction")
 
 
-def locomotion_fieldnames(contact_names, foot_frame_names, momentum: bool, forces: bool):
+def locomotion_fieldnames(contact_names, foot_frame_names, momentum: bool, forces: bool, ground_profile: bool = False):
     """Names of the rows of the tensors of a `LocomotionQuantities` block."""
     xyz = ("X", "Y", "Z")
     names = {"com": [f"Com.{e}" for e in xyz], "vcom": [f"ComVelocity.{e}" for e in xyz],
@@ -638,6 +638,8 @@ def locomotion_fieldnames(contact_names, foot_frame_names, momentum: bool, force
     if forces:
         names["contact_force_rel"] = [[f"{n}.{e}" for n in contact_names] for e in ("LinX", "LinY", "LinZ", "AngX", "AngY", "AngZ")]
         names["foot_force_vertical"] = [f"{n}.ForceVertical" for n in foot_frame_names]
+    if ground_profile:
+        names["contact_ground"] = [[f"{n}.{e}" for n in contact_names] for e in ("GroundHeight", "NormalX", "NormalY", "NormalZ")]
     return names
 
 
@@ -663,11 +665,24 @@ class LocomotionQuantities:
     instead of the engine's fields; `frames` must be a `FrameKinematics(state=...)` block of the same state; the lane's biased
     model is not applied.  A recorded trajectory carries no constraint multipliers: `forces=True` raises.  Where the state has
     no acceleration (`CentroidalState` built with `a` None), `zmp` is None: the reference's `ZeroMomentPoint.initialize` raises
-    in that case."""
+    in that case.
+
+    `ground_profile=True`: height-map ground with the constraint contact model, whose contact rows live in the local frame
+    [t0 t1 n] of the surface under each contact point (`FrameConstraint::setNormal`).  Every `refresh()` / `reset()` reads the
+    engine's current height map, its grid and its `ground_offset` field (`set_ground_heightmap`, `set_ground_offsets`; they may
+    be bound after the block is built and change between launches) and queries the ground under every contact point at the
+    lane's offset: `foot_force_vertical` is then the world vertical force, the third row of [t0 t1 n] on the multipliers of
+    every contact, and `ground_distance_min` the minimum of `(z - height) * normal_z` (`_MultiContactMinGroundDistance`,
+    compositions/locomotion.py:449-540).  `contact_ground` `[4][n_contacts][B]` holds the height and the unit normal under
+    every contact point (None without the option).  `contact_force_rel`, `force_vertical_max` and the friction reward stay in
+    the local contact frame, as in the reference; the other quantities do not look at the ground.  With no map bound the
+    results are the flat ones.  Not with `state=`: the reference evaluates the ground distance in TRUE mode only.
+    Without the option the block refuses an engine that has a height map bound when the block is built; a map bound LATER
+    (`WalkerVecEnv` binds its `ground_profile` in `reset()`) is not seen, and the flat formulas are then evaluated on it."""
 
     def __init__(self, engine, frames: "FrameKinematics", *, foot_frame_names="auto", zmp_reference_frame="LOCAL",
                  dcm_reference_frame="LOCAL", momentum_cutoff: Optional[float] = None, friction_cutoff: Optional[float] = None,
-                 momentum: bool = True, forces: bool = True, state=None) -> None:
+                 momentum: bool = True, forces: bool = True, state=None, ground_profile: bool = False) -> None:
         import ctypes as C
 
         from . import _abi, locomotion
@@ -676,6 +691,10 @@ class LocomotionQuantities:
         if not model.has_freeflyer:
             raise ValueError("Only legged robot with floating base are supported: the model has no free-flyer.")
         self._state, has_acceleration = None, True
+        self.ground_profile = bool(ground_profile)
+        if self.ground_profile and state is not None:
+            raise NotImplementedError("ground_profile=True with a reference state: the reference evaluates the distance to the "
+                                      "ground in TRUE mode only (`_MultiContactMinGroundDistance`)")
         if state is not None:
             if forces:
                 raise NotImplementedError("the contact force quantities of a reference state: a recorded trajectory carries no "
@@ -709,9 +728,9 @@ class LocomotionQuantities:
             raise NotImplementedError("the contact force quantities read the multipliers of the contact constraints "
                                       "(`lambda_c`): contacts.model = 'spring_damper' has none (pass forces=False for the "
                                       "other quantities)")
-        if engine._ground is not None:
+        if engine._ground is not None and not self.ground_profile:
             raise NotImplementedError("the locomotion quantities assume flat ground: on a height map the local contact frame "
-                                      "is the surface's")
+                                      "is the surface's (pass ground_profile=True)")
         self.plan = locomotion.build_plan(model, frames.frame_names, foot_frame_names=foot_frame_names,
                                           zmp_reference_frame=zmp_reference_frame, dcm_reference_frame=dcm_reference_frame)
         if self.momentum and frames.plan.modes[frames.index("root_joint")] != frames_.LOCAL:
@@ -733,6 +752,8 @@ class LocomotionQuantities:
         self.h_angular = new(3) if self.momentum else None
         self.contact_force_rel = new(6, nc) if self.forces else None
         self.foot_force_vertical = new(self.plan.n_feet) if self.forces else None
+        self.contact_ground = new(4, nc) if self.ground_profile else None
+        self._ground_io = _abi.LocomotionGround() if self.ground_profile else None
         rows = _abi.constraint_rows(model)
         self._flag_row, self._lambda_row = rows["n_bounds"], 2 * rows["n_bounds"]
         self._q_row = int(model.idx_q[1])
@@ -745,7 +766,7 @@ class LocomotionQuantities:
 
     @property
     def fieldnames(self):
-        return locomotion_fieldnames(self._eng.model.contacts, self.foot_frame_names, self.momentum, self.forces)
+        return locomotion_fieldnames(self._eng.model.contacts, self.foot_frame_names, self.momentum, self.forces, self.ground_profile)
 
     @property
     def force_vertical_max(self) -> torch.Tensor:
@@ -791,8 +812,19 @@ class LocomotionQuantities:
         io.lane_mask = None if mask is None else mask.data_ptr()
         for name in ("com", "vcom", "odom_pose", "zmp", "dcm", "h_angular", "contact_force_rel", "foot_force_vertical", "scalars"):
             setattr(io, name, ptr(getattr(self, name)))
-        self._check(self._L.jm_block_locomotion(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
-                                                self.momentum_cutoff or 0.0, self.friction_cutoff or 0.0, eng._stream()))
+        if not self.ground_profile:
+            self._check(self._L.jm_block_locomotion(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
+                                                    self.momentum_cutoff or 0.0, self.friction_cutoff or 0.0, eng._stream()))
+            return
+        # the engine's height map, grid and offsets as they are bound now
+        g, heights = self._ground_io, eng._ground
+        g.heights, g.offsets, g.contact_ground = ptr(heights), None, ptr(self.contact_ground)
+        if heights is not None:
+            g.ny, g.nx = int(heights.shape[0]), int(heights.shape[1])
+            g.x0, g.y0, g.dx, g.dy = eng._ground_grid
+            g.offsets = ptr(eng._fields.get("ground_offset"))
+        self._check(self._L.jm_block_locomotion_ground(self._plan, self._dtype, eng.batch_size, self._C.byref(io), self._C.byref(g),
+                                                       self.momentum_cutoff or 0.0, self.friction_cutoff or 0.0, eng._stream()))
 
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         """The quantities at the state of a new episode on the masked lanes (every lane without a mask); the other lanes

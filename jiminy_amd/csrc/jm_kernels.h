@@ -498,28 +498,12 @@ template<class T, class Tp> JM_DEV V3<T> contact_law_n(CPtr<T> P, V3<T> n, T dep
     }
     return f;
 }
-// world.groundProfile(x, y) -> height and unit normal out of the height map of the batch arguments
-// (`A`: anything with the height-map fields of BatchArgs -- the batch arguments or the constraint arguments)
-template<class T, class G> JM_DEV void ground_profile(const G & A, T x, T y, T & h, V3<T> & n)
+}  // namespace jm
+// world.groundProfile(x, y) as bilinear patches and the tangents of a contact constraint's local frame on it: shared with the
+// locomotion quantities (jm_locomotion.h)
+#include "jm_ground.h"
+namespace jm
 {
-    const int nx = A.ground_nx, ny = A.ground_ny;
-    T u = (x - A.ground_x0) / A.ground_dx, w = (y - A.ground_y0) / A.ground_dy;
-    const bool in_x = u >= T(0) && u <= T(nx - 1), in_y = w >= T(0) && w <= T(ny - 1);
-    u = fmin_(fmax_(u, T(0)), T(nx - 1));
-    w = fmin_(fmax_(w, T(0)), T(ny - 1));
-    int ix = (int)u, iy = (int)w;
-    ix = ix > nx - 2 ? nx - 2 : ix; iy = iy > ny - 2 ? ny - 2 : iy;
-    ix = ix < 0 ? 0 : ix; iy = iy < 0 ? 0 : iy;
-    const T fx = u - T(ix), fy = w - T(iy);
-    const T h00 = A.ground_h[iy * nx + ix], h10 = A.ground_h[iy * nx + ix + 1];
-    const T h01 = A.ground_h[(iy + 1) * nx + ix], h11 = A.ground_h[(iy + 1) * nx + ix + 1];
-    h = (T(1) - fy) * ((T(1) - fx) * h00 + fx * h10) + fy * ((T(1) - fx) * h01 + fx * h11);
-    // outside the grid the ground continues flat (height of the nearest edge sample, no slope across the edge)
-    const T dhdx = in_x ? ((T(1) - fy) * (h10 - h00) + fy * (h11 - h01)) / A.ground_dx : T(0);
-    const T dhdy = in_y ? ((T(1) - fx) * (h01 - h00) + fx * (h11 - h10)) / A.ground_dy : T(0);
-    const T inv = T(1) / sqrt_(dhdx * dhdx + dhdy * dhdy + T(1));
-    n = {-dhdx * inv, -dhdy * inv, inv};
-}
 // Local frame of a contact constraint on the ground surface, in ROOT coordinates: the reference expresses the rows
 // of a FrameConstraint (x, y, z, rotation about z) in `rotationLocal_` = [t0 t1 n] built from the ground normal n under
 // the contact point (FrameConstraint::setNormal, frame_constraint.cc:62-68: t1 = normalize(n x e_x), t0 = t1 x n), and
@@ -541,10 +525,8 @@ template<bool GND, class T, class G> JM_DEV M3<T> contact_frame(const G & g, con
     V3<T> n;
     ground_profile(g, pW.x, pW.y, hG, n);
     depth = (pW.z - hG) * n.z;
-    // t1 = normalize(n x e_x) = (0, n.z, -n.y) / |.|, t0 = t1 x n
-    const T inv = rsqrt_(n.z * n.z + n.y * n.y);
-    const V3<T> t1 = {T(0), n.z * inv, -n.y * inv};
-    const V3<T> t0 = cross(t1, n);
+    V3<T> t0, t1;
+    ground_tangents(n, t0, t1);
     return {t0.x * R1.m00 + t0.y * R1.m10 + t0.z * R1.m20, t0.x * R1.m01 + t0.y * R1.m11 + t0.z * R1.m21, t0.x * R1.m02 + t0.y * R1.m12 + t0.z * R1.m22,
             t1.x * R1.m00 + t1.y * R1.m10 + t1.z * R1.m20, t1.x * R1.m01 + t1.y * R1.m11 + t1.z * R1.m21, t1.x * R1.m02 + t1.y * R1.m12 + t1.z * R1.m22,
             n.x * R1.m00 + n.y * R1.m10 + n.z * R1.m20, n.x * R1.m01 + n.y * R1.m11 + n.z * R1.m21, n.x * R1.m02 + n.y * R1.m12 + n.z * R1.m22};

@@ -394,6 +394,39 @@ int32_t jm_block_locomotion(const jm_locomotion_plan * p, int32_t dtype, int64_t
     });
 }
 
+int32_t jm_block_locomotion_ground(const jm_locomotion_plan * p, int32_t dtype, int64_t B, const jm_locomotion_io * io,
+                                   const jm_locomotion_ground * g, double momentum_cutoff, double friction_cutoff, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_locomotion_ground: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_locomotion_ground: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_locomotion_ground: bad dtype");
+    std::string why;
+    if (!jm::locomotion_ground_check(g, io, why)) return fail(JM_EINVAL, why);
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        jm::LocoIO<T> a{(const T *)io->centroidal, (const T *)io->q_root, (const T *)io->model_lane, (const T *)io->con_lambda,
+                        io->con_flags, (const T *)io->v_avg, (const T *)io->quat_no_yaw, (const T *)io->pose, io->lane_mask,
+                        (T *)io->com, (T *)io->vcom, (T *)io->odom_pose, (T *)io->zmp, (T *)io->dcm, (T *)io->h_angular,
+                        (T *)io->contact_force_rel, (T *)io->foot_force_vertical, (T *)io->scalars};
+        if (!g || !g->heights)
+        {
+            // flat ground: the kernel of jm_block_locomotion itself, so that the outputs are equal bit for bit
+            hipLaunchKernelGGL((jm::k_locomotion<T>), grid, dim3(256), 0, s, it, dt, a, momentum_cutoff, friction_cutoff, (long long)B);
+            if (g && g->contact_ground)
+                hipLaunchKernelGGL((jm::k_locomotion_flat_ground<T>), grid, dim3(256), 0, s, it, (T *)g->contact_ground, io->lane_mask,
+                                   (long long)B);
+            return;
+        }
+        a.ground_h = (const T *)g->heights; a.ground_nx = g->nx; a.ground_ny = g->ny;
+        a.ground_x0 = (T)g->x0; a.ground_y0 = (T)g->y0; a.ground_dx = (T)g->dx; a.ground_dy = (T)g->dy;
+        a.ground_off = (const T *)g->offsets;
+        a.contact_ground = (T *)g->contact_ground;
+        hipLaunchKernelGGL((jm::k_locomotion<T, true>), grid, dim3(256), 0, s, it, dt, a, momentum_cutoff, friction_cutoff, (long long)B);
+    });
+}
+
 int32_t jm_actuation_plan_create(const jm_actuation_desc * desc, jm_actuation_plan ** out)
 {
     return plan_create("jm_actuation_plan_create", desc, out, jm::actuation_pack);

@@ -17,6 +17,12 @@
 //   normalize_vertical_forces                     quantities/locomotion.py:1272-1312 (flat ground: every vertical transform is e_z)
 //   min_depth                                     compositions/locomotion.py:450-473 (flat ground: heights 0, normals e_z)
 //   radial_basis_function, CUTOFF_ESP             compositions/mixin.py:17-66
+// On a height map (`locomotion_lane<T, true>` with `ground_h` bound; jm_ground.h):
+//   MultiFootNormalizedForceVertical.refresh      quantities/locomotion.py:1468-1481: the vertical transform of a contact is the
+//                                                 third row of its constraint's `local_rotation` = [t0 t1 n]
+//                                                 (FrameConstraint::setNormal, frame_constraint.cc:62-68)
+//   _MultiContactMinGroundDistance.refresh        compositions/locomotion.py:527-540: height and normal of the ground under
+//                                                 every contact point, min((z - height) * normal_z)
 //
 // All lanes interpret the same plan tables: their reads are indexed by loop counters only and become scalar loads.
 #pragma once
@@ -25,6 +31,7 @@
 #include <vector>
 
 #include "jm_frames.h"
+#include "jm_ground.h"
 #include "../../include/jiminy_hip.h"
 
 namespace jm
@@ -91,6 +98,19 @@ inline bool locomotion_pack(const jm_locomotion_desc * d, std::vector<int32_t> &
     return true;
 }
 
+// Validate the ground description of one launch (`jm_block_locomotion_ground`); null or without heights: flat ground.
+inline bool locomotion_ground_check(const jm_locomotion_ground * g, const jm_locomotion_io * io, std::string & why)
+{
+    const std::string who = "jm_block_locomotion_ground: ";
+    if (!g || !g->heights) return true;
+    if (g->nx < 2 || g->ny < 2) { why = who + "the height map needs at least 2 x 2 samples"; return false; }
+    if (!std::isfinite(g->x0) || !std::isfinite(g->y0)) { why = who + "the origin of the height map is not finite"; return false; }
+    if (!std::isfinite(g->dx) || !std::isfinite(g->dy) || !(g->dx > 0.0) || !(g->dy > 0.0))
+    { why = who + "the spacings of the height map must be positive and finite"; return false; }
+    if (!io->pose) { why = who + "the queries of the height map read `pose`"; return false; }
+    return true;
+}
+
 // the inputs and outputs of one launch (device pointers of the kernel's scalar type but `con_flags`); every one may be null
 template<class T> struct LocoIO
 {
@@ -107,6 +127,13 @@ template<class T> struct LocoIO
     T * contact_force_rel;     // [6][n_contacts][B]
     T * foot_force_vertical;   // [n_feet][B]
     T * scalars;               // [4][B]
+    // the ground under the contact points (`locomotion_lane<T, true>` only; null `ground_h`: flat ground): the height map in
+    // the fields of `ground_profile` (jm_ground.h), the lanes' offsets of its queries and what it gives under every contact
+    const T * ground_h = nullptr;       // [ground_ny][ground_nx]
+    int ground_nx = 0, ground_ny = 0;
+    T ground_x0 = T(0), ground_y0 = T(0), ground_dx = T(1), ground_dy = T(1);
+    const T * ground_off = nullptr;     // [2][B] or null
+    T * contact_ground = nullptr;       // [4][n_contacts][B] height, unit normal
 };
 
 JM_DEV double loco_pow(double x, double y) { return ::pow(x, y); }
@@ -128,14 +155,35 @@ template<class T> JM_DEV T loco_rbf(T sq_norm, T cutoff)
     return loco_pow(T(LOCO_CUTOFF_ESP), sq_norm / loco_pow(cutoff, T(2)));
 }
 
-// All quantities of one lane.  A part whose inputs or output are null is skipped.
-template<class T>
+// Height and unit normal of the ground under the frame of column `col` of `pose`, queried at the lane's offset; `z`: the
+// world height of the frame
+template<class T> JM_DEV void loco_ground_under(const LocoIO<T> & io, int col, long long KB, long long B, long long lane, T & z, T & h,
+                                                V3<T> & n)
+{
+    const T * p = io.pose + (long long)col * B + lane;
+    T x = p[0], y = p[KB];
+    z = p[2 * KB];
+    if (io.ground_off) { x += io.ground_off[lane]; y += io.ground_off[B + lane]; }
+    ground_profile(io, x, y, h, n);
+}
+
+// `contact_ground` of the flat ground: height 0 and normal e_z under every contact point
+template<class T> JM_DEV void loco_flat_contact_ground(T * contact_ground, int nc, long long B, long long lane)
+{
+    for (long long r = 0; r < 4LL * nc; ++r) contact_ground[r * B + lane] = r < 3LL * nc ? T(0) : T(1);
+}
+
+// All quantities of one lane.  A part whose inputs or output are null is skipped.  GND: on the height map of `io` where one
+// is bound (its queries read `pose`); GND = false is the flat ground at compile time.
+template<class T, bool GND = false>
 JM_DEV void locomotion_lane(const int32_t * __restrict__ it, const double * __restrict__ dt, const LocoIO<T> & io, T momentum_cutoff,
                             T friction_cutoff, long long B, long long lane)
 {
     const int nc = it[0], zmp_frame = it[2], dcm_frame = it[3], K = it[4], root = it[5], nj = it[6];
     const long long KB = (long long)K * B;
     const int32_t * con = it + LOCO_HEAD_INTS;
+    bool ground = false;
+    if constexpr (GND) ground = io.ground_h && io.pose;
     // mass of the robot (`pinocchio_data.mass[0]`) and its weight (:981-983)
     T mass = (T)dt[LOCO_MASS];
     if (io.model_lane)
@@ -237,7 +285,21 @@ JM_DEV void locomotion_lane(const int32_t * __restrict__ it, const double * __re
                 foot = f;
                 foot_sum = T(0);
             }
-            foot_sum += lz;
+            if constexpr (GND)
+            {
+                // the world vertical force: the third row of [t0 t1 n] on the local multipliers (:1308)
+                T vz = lz;
+                if (ground)
+                {
+                    T z, h;
+                    V3<T> n, t0, t1;
+                    loco_ground_under(io, con[2 * c + 1], KB, B, lane, z, h, n);
+                    ground_tangents(n, t0, t1);
+                    vz = t0.z * lx + t1.z * ly + n.z * lz;
+                }
+                foot_sum += vz;
+            }
+            else foot_sum += lz;
         }
         if (foot >= 0 && io.foot_force_vertical) io.foot_force_vertical[(long long)foot * B + lane] = foot_sum / weight;
         if (io.scalars)
@@ -247,6 +309,30 @@ JM_DEV void locomotion_lane(const int32_t * __restrict__ it, const double * __re
         }
     }
 
+    // `min_depth` on the height map: (z - height) * normal_z of the ground under every contact frame (:472)
+    if constexpr (GND)
+        if (ground && (io.scalars || io.contact_ground))
+        {
+            const long long NB = (long long)nc * B;
+            T d_min = T(0);
+            for (int c = 0; c < nc; ++c)
+            {
+                T z, h;
+                V3<T> n;
+                loco_ground_under(io, con[2 * c + 1], KB, B, lane, z, h, n);
+                if (io.contact_ground)
+                {
+                    T * o = io.contact_ground + (long long)c * B + lane;
+                    o[0] = h; o[NB] = n.x; o[2 * NB] = n.y; o[3 * NB] = n.z;
+                }
+                const T d = (z - h) * n.z;
+                d_min = c == 0 ? d : fmin_(d_min, d);
+            }
+            if (io.scalars) io.scalars[(long long)LOCO_GROUND_DISTANCE_MIN * B + lane] = d_min;
+            return;
+        }
+    if constexpr (GND)
+        if (io.contact_ground) loco_flat_contact_ground(io.contact_ground, nc, B, lane);       // (no map bound)
     // `min_depth` on flat ground: the lowest contact frame
     if (io.pose && io.scalars)
     {
@@ -261,14 +347,26 @@ JM_DEV void locomotion_lane(const int32_t * __restrict__ it, const double * __re
 }
 
 #ifndef JM_HOST_EMU
-template<class T>
+template<class T, bool GND = false>
 __global__ void __launch_bounds__(256) k_locomotion(const int32_t * __restrict__ it, const double * __restrict__ dt, const LocoIO<T> io,
                                                      double momentum_cutoff, double friction_cutoff, long long B)
 {
     const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
     if (lane >= B) return;
     if (io.lane_mask && !io.lane_mask[lane]) return;
-    locomotion_lane<T>(it, dt, io, (T)momentum_cutoff, (T)friction_cutoff, B, lane);
+    locomotion_lane<T, GND>(it, dt, io, (T)momentum_cutoff, (T)friction_cutoff, B, lane);
+}
+
+// `contact_ground` where no map is bound: next to a launch of `k_locomotion<T>`, whose outputs the flat ground's must equal
+// bit for bit
+template<class T>
+__global__ void __launch_bounds__(256) k_locomotion_flat_ground(const int32_t * __restrict__ it, T * contact_ground,
+                                                                 const uint8_t * __restrict__ lane_mask, long long B)
+{
+    const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (lane >= B) return;
+    if (lane_mask && !lane_mask[lane]) return;
+    loco_flat_contact_ground(contact_ground, it[0], B, lane);
 }
 #endif
 }  // namespace jm

@@ -448,6 +448,9 @@ class WalkerVecEnv(VecJiminyEnv):
         #   impact_force=(max_force_rel, grace_period) ≙ `ImpactForceTermination` (:582-620)
         #   reward_mixture['momentum'] / ['friction']  ≙ `MinimizeAngularMomentumReward` / `MinimizeFrictionReward` (:257-315),
         #                                              weights on the reward rows of the block's `momentum_cutoff` / `friction_cutoff`
+        # with an environment-level `ground_profile` pass `locomotion_quantities=dict(ground_profile=True, ...)`: the block then
+        # reads the height map and the lanes' patch offsets at every launch (the map is bound in `reset()`, after the block is
+        # built); without it the block evaluates the flat formulas on that ground without a word
         # optional `blocks.ActuatedJointQuantities` (its constructor's keywords; `step_dt` is the environment's), reset with the
         # other two blocks, refreshed once per environment step and exposed as `actuation`; what reads it:
         #   mechanical_safety=(position_margin, velocity_max, grace_period)  ≙ `MechanicalSafetyTermination`
