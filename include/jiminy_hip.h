@@ -1176,6 +1176,61 @@ int32_t jm_trackrewards_plan_destroy(jm_trackrewards_plan * plan);
 int32_t jm_block_tracking_rewards(const jm_trackrewards_plan * plan, int32_t dtype, int64_t batch_size, const jm_trackrewards_io * io,
                                   const double * cutoff, void * stream);
 
+/* ---- Projected support polygon: the 2D convex hull of every candidate contact point of a legged robot, its barycenter, the
+ * signed distance of the ZMP from its border and the robustness reward on it; batched, one lane = one environment, one
+ * launch per refresh.  New symbols only: no existing structure or signature changed with them.  Reference:
+ * python/gym_jiminy/toolbox/gym_jiminy/toolbox/math/qhull.py:52-224 and :396-457, quantities/locomotion.py:22-239,
+ * compositions/locomotion.py:15-115, restated operation for operation (csrc/jm_support.h).  The reference's host-side pruning
+ * of the contact points by the 3D hull of their body is not built: every point of the plan is a candidate.
+ * jm_support_desc: the plan (host array, copied by jm_support_plan_create).  `n_frames` = K, the number of columns of the
+ *   `pose` tensor of the frame kinematics block; per candidate point, in the model's contact order, the column of its frame
+ *   (`point_column`); `reference_frame` 0 (LOCAL: every point goes through `translate_position_odom` with the lane's
+ *   `odom_pose`) or 1 (LOCAL_WORLD_ALIGNED: the world coordinates as they are).  jm_support_plan_create validates the
+ *   description (JM_EINVAL + jm_last_error, before any device call: null array, 1 <= n_points <= 16, n_points <= n_frames,
+ *   columns inside [0, n_frames), no column twice, a frame other than the two) and uploads it; the launch then allocates,
+ *   copies and synchronises nothing.
+ * jm_support_io: the device pointers of one launch, arrays `[rows][B]` of the scalar type `dtype` (the two index outputs
+ *   int32).  Every pointer may be NULL: the outputs that need it are then not written.  Inputs: `pose` `[7][K][B]` (rows 0
+ *   and 1 are read); `odom_pose` `[3][B]` and `zmp` `[2][B]` of the locomotion quantities block, `zmp` in the plan's
+ *   reference frame (LOCAL without `odom_pose`: nothing is written); `lane_mask` (uint8 `[B]`, NULL: every lane; other lanes
+ *   are not touched).  Outputs:
+ *     n_vertices               the number of vertices of the hull
+ *     vertex_index[16]         their indices into `point_column`, in the reference's order (`compute_convex_hull_vertices`:
+ *                              the sorted order itself with 3 points or fewer, else the upper chain then the lower chain); -1
+ *                              from `n_vertices` on
+ *     vertices[2][16]          their coordinates; NaN from `n_vertices` on
+ *     center[2]                `ConvexHull2D.center`: the mean of the vertices
+ *     scalars[2]               0 stability_margin = minus `ConvexHull2D.get_distance_to_point(zmp)`, -inf where `zmp[0]` is NaN
+ *                              (`StabilityMarginProjectedSupportPolygon`); 1 reward_robustness = `sigmoid_normalization(margin,
+ *                              -cutoff_outer, cutoff_inner, True)` (`MaximizeRobustness`), written where both cutoffs are
+ *                              positive.  Without `zmp` neither row is written.
+ * jm_block_support_polygon: a negative or non-finite cutoff is JM_EINVAL.  A lane whose inputs are NaN or infinite
+ *   terminates like any other, with `n_vertices` in [0, 16], indices in [-1, n_points) and an arbitrary margin. */
+typedef struct jm_support_desc
+{
+    int32_t n_frames;
+    int32_t n_points;
+    int32_t reference_frame;
+    const int32_t * point_column;       /* [n_points] */
+} jm_support_desc;
+typedef struct jm_support_io
+{
+    const void * pose;
+    const void * odom_pose;
+    const void * zmp;
+    const uint8_t * lane_mask;
+    int32_t * n_vertices;
+    int32_t * vertex_index;
+    void * vertices;
+    void * center;
+    void * scalars;
+} jm_support_io;
+typedef struct jm_support_plan jm_support_plan;
+int32_t jm_support_plan_create(const jm_support_desc * desc, jm_support_plan ** out);
+int32_t jm_support_plan_destroy(jm_support_plan * plan);
+int32_t jm_block_support_polygon(const jm_support_plan * plan, int32_t dtype, int64_t batch_size, const jm_support_io * io,
+                                 double cutoff_inner, double cutoff_outer, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

@@ -219,6 +219,19 @@ class TrackRewardsIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in TRACKREWARDS_IO_FIELDS]
 
 
+class SupportDesc(C.Structure):
+    """jm_support_desc: the plan of the projected support polygon (jiminy_amd.support builds it)."""
+    _fields_ = [("n_frames", C.c_int32), ("n_points", C.c_int32), ("reference_frame", C.c_int32), ("point_column", _pi)]
+
+
+SUPPORT_IO_FIELDS = ("pose", "odom_pose", "zmp", "lane_mask", "n_vertices", "vertex_index", "vertices", "center", "scalars")
+
+
+class SupportIO(C.Structure):
+    """jm_support_io: the device pointers of one launch of jm_block_support_polygon, each or NULL."""
+    _fields_ = [(name, C.c_void_p) for name in SUPPORT_IO_FIELDS]
+
+
 class CentroidalDesc(C.Structure):
     """jm_centroidal_desc: the plan of the centroidal quantities of a state (jiminy_amd.centroidal builds it)."""
     _fields_ = [

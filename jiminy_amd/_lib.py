@@ -61,6 +61,7 @@ ABI_SYMBOLS = (
     "jm_trajectory_plan_create", "jm_trajectory_plan_destroy", "jm_block_trajectory_state",
     "jm_centroidal_plan_create", "jm_centroidal_plan_destroy", "jm_block_centroidal_state",
     "jm_trackrewards_plan_create", "jm_trackrewards_plan_destroy", "jm_block_tracking_rewards",
+    "jm_support_plan_create", "jm_support_plan_destroy", "jm_block_support_polygon",
 )
 
 
@@ -150,6 +151,9 @@ class HipLibrary:
         L.jm_trackrewards_plan_create.argtypes = [C.POINTER(_abi.TrackRewardsDesc), C.POINTER(vp)]
         L.jm_trackrewards_plan_destroy.argtypes = [vp]
         L.jm_block_tracking_rewards.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrackRewardsIO), dp, vp]
+        L.jm_support_plan_create.argtypes = [C.POINTER(_abi.SupportDesc), C.POINTER(vp)]
+        L.jm_support_plan_destroy.argtypes = [vp]
+        L.jm_block_support_polygon.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.SupportIO), C.c_double, C.c_double, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

@@ -62,6 +62,11 @@ launch per refresh (csrc/jm_centroidal.h) driven by a plan that jiminy_amd/centr
 joint positions): each quantity on the true side and on the reference side and the radial basis function of their difference,
 from the tensors of the blocks above.  One HIP launch per refresh (csrc/jm_trackrewards.h) driven by a plan that
 jiminy_amd/trackrewards.py builds; specification: tests/golden/ref_tracking_rewards.npz.
+
+`SupportPolygon` gives the projected support polygon (the 2D convex hull of every contact point, at most 16), its barycenter,
+the stability margin (the signed distance of the ZMP from its border) and the robustness reward on it, from the `pose` of a
+`FrameKinematics` and the `zmp` / `odom_pose` of a `LocomotionQuantities`.  One HIP launch per refresh (csrc/jm_support.h)
+driven by a plan that jiminy_amd/support.py builds; specification: tests/golden/ref_support.npz.
 """
 from __future__ import annotations
 
@@ -1116,6 +1121,145 @@ class FootPoseQuantities:
         if plan:
             try:
                 self._L.jm_footposes_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+def support_fieldnames(contact_names):
+    """Names of the rows of the tensors of a `SupportPolygon` block (`vertex_index` counts in `contact_names`)."""
+    from .support import MAX_POINTS, SCALARS
+    return {"n_vertices": ["SupportPolygon.VertexCount"], "vertex_index": [f"SupportPolygon.Vertex{k}" for k in range(MAX_POINTS)],
+            "vertices": [[f"SupportPolygon.Vertex{k}.{e}" for k in range(MAX_POINTS)] for e in ("X", "Y")],
+            "center": ["SupportPolygon.CenterX", "SupportPolygon.CenterY"], "scalars": list(SCALARS),
+            "points": list(contact_names)}
+
+
+class SupportPolygon:
+    """The projected support polygon of the reference's toolbox per lane (toolbox/quantities/locomotion.py:22-239,
+    toolbox/math/qhull.py, toolbox/compositions/locomotion.py:15-115), from the `pose` of a `FrameKinematics` and the `zmp` /
+    `odom_pose` of a `LocomotionQuantities`: `n_vertices` `[B]` and `vertex_index` `[16][B]` (int32; indices into the model's
+    contact points in the reference's vertex order, -1 behind the last vertex), `vertices` `[2][16][B]` (NaN behind the last
+    vertex) and `center` `[2][B]` ≙ `ProjectedSupportPolygon` (`ConvexHull2D.indices`, `.vertices`, `.center`); `scalars`
+    `[2][B]`, rows `support.SCALARS`: `stability_margin` ≙ `StabilityMarginProjectedSupportPolygon` (minus the signed distance
+    of the ZMP from the border; -inf where the ZMP is NaN, a robot in free fall) and `reward_robustness` ≙ `MaximizeRobustness`
+    with `cutoff_inner` / `cutoff_outer` (both None: the row stays zero and the property raises).
+
+    `frames`: the `FrameKinematics` block of the same engine holding every contact frame; `locomotion`: the
+    `LocomotionQuantities` block of the same engine and the same `frames`; refresh both first.  `reference_frame` ('LOCAL' or
+    'LOCAL_WORLD_ALIGNED') defaults to the frame of `locomotion.zmp`.  The margin is evaluated in the one frame the block has:
+    the polygon and the ZMP must be in the same frame, another `reference_frame` than `locomotion`'s `zmp_reference_frame`
+    raises (unless `locomotion.zmp` is None).  The reference evaluates the margin in LOCAL_WORLD_ALIGNED; in LOCAL the margin
+    equals that value up to round-off, because the map into the odometry frame is rigid and keeps distances.  Where
+    `locomotion.zmp` is None (a reference state without accelerations) the block gives the polygon only and `scalars` is None.
+    A pair of `state=` blocks (`QuantityEvalMode.REFERENCE`) works as it is: the block only reads their tensors.
+
+    Deviations.  The reference prunes, on the host, the contact points that are not vertices of the 3D hull of their body, which
+    does not change the polygon; here every contact point is a candidate, and a model with more than 16 contact points is
+    refused.  A cutoff of zero where the other is given is refused: the reference accepts it and would divide 0 by 0 at a
+    margin of exactly 0.  One cutoff without the other is refused as well (the reference takes both).
+
+    `refresh()` is one launch on the engine's stream, without allocation, copy or synchronisation; `reset(lane_mask)` evaluates
+    the masked lanes (every lane without a mask) and keeps the others bit for bit.  The tensors never change identity."""
+
+    def __init__(self, engine, frames: "FrameKinematics", locomotion: "LocomotionQuantities", *, reference_frame=None,
+                 cutoff_inner: Optional[float] = None, cutoff_outer: Optional[float] = None) -> None:
+        import ctypes as C
+
+        from . import _abi, support
+        from .locomotion import odometry_frame
+        support.check_model(engine.model)
+        if frames._eng is not engine:
+            raise ValueError("the frame kinematics block belongs to another engine")
+        if locomotion._eng is not engine:
+            raise ValueError("the locomotion quantities block belongs to another engine")
+        if locomotion._frames is not frames:
+            raise ValueError("the locomotion quantities block reads another frame kinematics block")
+        for cutoff in (cutoff_inner, cutoff_outer):
+            if cutoff is not None and not float(cutoff) >= 0.0:
+                raise ValueError("The inner and outer cutoff thresholds must both be positive.")
+        if (cutoff_inner is None) != (cutoff_outer is None):
+            raise ValueError("the robustness reward needs cutoff_inner and cutoff_outer together")
+        if cutoff_inner is not None and (float(cutoff_inner) == 0.0 or float(cutoff_outer) == 0.0):
+            raise ValueError("a cutoff of zero is refused: the reward would divide 0 by 0 at a margin of 0")
+        zmp_frame = int(locomotion.plan.arrays["zmp_frame"])
+        frame = zmp_frame if reference_frame is None else odometry_frame(reference_frame)
+        self.plan = support.build_plan(engine.model, frames.frame_names, frame)
+        if locomotion.zmp is not None and frame != zmp_frame:
+            names = ("LOCAL", "LOCAL_WORLD_ALIGNED")
+            raise ValueError(f"reference_frame {names[frame]} differs from the zmp_reference_frame {names[zmp_frame]} of the "
+                             "locomotion quantities block: the margin is evaluated in one frame")
+        self._C = C
+        self._eng, self._frames, self._locomotion = engine, frames, locomotion
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.reference_frame = frame
+        self.contact_names = list(self.plan.contact_names)
+        self.cutoff_inner = None if cutoff_inner is None else float(cutoff_inner)
+        self.cutoff_outer = None if cutoff_outer is None else float(cutoff_outer)
+        B, M = engine.batch_size, support.MAX_POINTS
+        new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
+        self.n_vertices, self.vertex_index = new(dtype=torch.int32), new(M, dtype=torch.int32)
+        self.vertices, self.center = new(2, M), new(2)
+        self.scalars = new(2) if locomotion.zmp is not None else None
+        self._io = _abi.SupportIO()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_support_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    @property
+    def fieldnames(self):
+        return support_fieldnames(self.contact_names)
+
+    @property
+    def stability_margin(self) -> torch.Tensor:
+        if self.scalars is None:
+            raise ValueError("the block has no margin: the locomotion quantities block has no zmp")
+        return self.scalars[0]
+
+    @property
+    def reward_robustness(self) -> torch.Tensor:
+        if self.scalars is None or self.cutoff_inner is None:
+            raise ValueError("the block has no reward: build it with cutoff_inner and cutoff_outer (and a zmp)")
+        return self.scalars[1]
+
+    def _launch(self, mask: Optional[torch.Tensor]) -> None:
+        eng, io, loco = self._eng, self._io, self._locomotion
+
+        def ptr(t: Optional[torch.Tensor], dtype=None):
+            if t is None:
+                return None
+            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
+                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+            return t.data_ptr()
+        io.pose, io.odom_pose, io.zmp = ptr(self._frames.pose), ptr(loco.odom_pose), ptr(loco.zmp)
+        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.n_vertices, io.vertex_index = ptr(self.n_vertices, torch.int32), ptr(self.vertex_index, torch.int32)
+        io.vertices, io.center, io.scalars = ptr(self.vertices), ptr(self.center), ptr(self.scalars)
+        self._check(self._L.jm_block_support_polygon(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
+                                                     self.cutoff_inner or 0.0, self.cutoff_outer or 0.0, eng._stream()))
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        """The quantities at the state of a new episode on the masked lanes (every lane without a mask); the other lanes
+        keep every tensor bit for bit.  Call it after the reset of `frames` and of `locomotion`."""
+        mask = None
+        if lane_mask is not None:
+            mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (self._eng.batch_size,):
+                raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
+        self._launch(mask)
+
+    def refresh(self) -> None:
+        """One launch on the engine's stream, behind the refresh of `frames` and of `locomotion`."""
+        self._launch(None)
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_support_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state and of the tracking rewards, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state, of the tracking rewards and of the support polygon, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@
 #include "jm_trajectory.h"
 #include "jm_centroidal.h"
 #include "jm_trackrewards.h"
+#include "jm_support.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -138,6 +139,12 @@ struct jm_centroidal_plan
 
 // the tracking rewards (jm_trackrewards.h)
 struct jm_trackrewards_plan
+{
+    DevicePlan dev;
+};
+
+// the projected support polygon (jm_support.h)
+struct jm_support_plan
 {
     DevicePlan dev;
 };
@@ -608,6 +615,34 @@ int32_t jm_block_tracking_rewards(const jm_trackrewards_plan * p, int32_t dtype,
                                 (const T *)io->dcm_reference, (const T *)io->position, (const T *)io->position_reference, io->lane_mask,
                                 (T *)io->value, (T *)io->reference, (T *)io->rewards};
         hipLaunchKernelGGL((jm::k_tracking_rewards<T>), grid, dim3(256), 0, s, it, a, c, (long long)B);
+    });
+}
+
+int32_t jm_support_plan_create(const jm_support_desc * desc, jm_support_plan ** out)
+{
+    return plan_create("jm_support_plan_create", desc, out, jm::support_pack);
+}
+
+int32_t jm_support_plan_destroy(jm_support_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_support_polygon(const jm_support_plan * p, int32_t dtype, int64_t B, const jm_support_io * io, double cutoff_inner,
+                                 double cutoff_outer, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_support_polygon: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_support_polygon: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_support_polygon: bad dtype");
+    std::string why;
+    if (!jm::support_cutoffs_check(cutoff_inner, cutoff_outer, why)) return fail(JM_EINVAL, why);
+    const int32_t * it = p->dev.it;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        const jm::SupportIO<T> a{(const T *)io->pose, (const T *)io->odom_pose, (const T *)io->zmp, io->lane_mask, io->n_vertices,
+                                 io->vertex_index, (T *)io->vertices, (T *)io->center, (T *)io->scalars};
+        hipLaunchKernelGGL((jm::k_support_polygon<T>), grid, dim3(256), 0, s, it, a, cutoff_inner, cutoff_outer, (long long)B);
     });
 }
 

@@ -432,7 +432,7 @@ class WalkerVecEnv(VecJiminyEnv):
                  locomotion_quantities: Optional[Dict[str, Any]] = None, actuated_joints: Optional[Dict[str, Any]] = None,
                  foot_poses: Optional[Dict[str, Any]] = None, trajectory_tracking: Optional[Dict[str, Any]] = None,
                  trajectory_database: Optional[Dict[str, Any]] = None, tracking_rewards: Optional[Dict[str, Any]] = None,
-                 **kw: Any) -> None:
+                 support_polygon: Optional[Dict[str, Any]] = None, **kw: Any) -> None:
         super().__init__(*args, **kw)
         self.reward_mixture = dict(reward_mixture or {"survival": 1.0})
         # optional `blocks.FrameKinematics` (its constructor's keywords, `frame_names` included), refreshed once per
@@ -500,9 +500,14 @@ class WalkerVecEnv(VecJiminyEnv):
         #                                              `TrackingActuatedJointPositionsReward` (compositions/generic.py:125-150),
         #                                              weights on the reward rows of the block
         #   reward_mixture['foot_force_distribution'] is refused: a recorded trajectory carries no constraint multipliers.
+        # optional `blocks.SupportPolygon` (its constructor's keywords: `cutoff_inner`, `cutoff_outer`, `reference_frame`), reset
+        # and refreshed directly behind `locomotion`, which it needs, and exposed as `support`; what reads it:
+        #   reward_mixture['robustness']               ≙ `MaximizeRobustness` (toolbox/compositions/locomotion.py:51-115), weight on
+        #                                              the reward row of the block's `cutoff_inner` and `cutoff_outer`
         self.frames = self.locomotion = self.actuation = self.foot_poses = self.tracking = None
         self.trajectory = self._reference_frames = self._reference_foot_poses = None
         self.tracking_rewards = self._reference_centroidal = self._reference_locomotion = None
+        self.support = None
         self._terminations = dict(terminations or {})
         tracking_terms = {"drift_odom_position": "odometry_horizon", "drift_odom_orientation": "odometry_horizon",
                           "shift_foot_positions": "foot_horizon", "shift_foot_orientations": "foot_horizon",
@@ -523,6 +528,15 @@ class WalkerVecEnv(VecJiminyEnv):
         elif {"momentum", "friction"} & set(self.reward_mixture):
             raise ValueError("the momentum and friction reward terms read the locomotion quantities block: give "
                              "locomotion_quantities as well")
+        if support_polygon is not None:
+            if locomotion_quantities is None:
+                raise ValueError("the support polygon reads the locomotion quantities block: give locomotion_quantities as well")
+            if "robustness" in self.reward_mixture and (support_polygon.get("cutoff_inner") is None or
+                                                        support_polygon.get("cutoff_outer") is None):
+                raise ValueError("reward_mixture['robustness'] needs support_polygon['cutoff_inner'] and "
+                                 "support_polygon['cutoff_outer']")
+        elif "robustness" in self.reward_mixture:
+            raise ValueError("the robustness reward term reads the support polygon block: give support_polygon as well")
         if {"mechanical_safety", "power_consumption"} & set(self._terminations) and actuated_joints is None:
             raise ValueError("the mechanical_safety and power_consumption terminations read the actuated-joint quantities "
                              "block: give actuated_joints as well")
@@ -626,6 +640,8 @@ class WalkerVecEnv(VecJiminyEnv):
             if locomotion_quantities is not None:
                 self.engine.enable_output("centroidal")
                 self.locomotion = blocks.LocomotionQuantities(self.engine, self.frames, **locomotion_quantities)
+                if support_polygon is not None:
+                    self.support = blocks.SupportPolygon(self.engine, self.frames, self.locomotion, **support_polygon)
             if set(self._terminations) - no_frames:
                 self._frame_root = self.frames.index("root_joint")
                 self._frame_contacts = torch.tensor([self.frames.index(n) for n in self.model.contacts], dtype=torch.long, device=self.device)
@@ -794,6 +810,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(None)
         if self.locomotion is not None:
             self.locomotion.reset(None)
+        if self.support is not None:
+            self.support.reset(None)
         if self.trajectory is not None:
             self._query_trajectory(None)
         if self.foot_poses is not None:
@@ -814,6 +832,8 @@ class WalkerVecEnv(VecJiminyEnv):
             self.frames.reset(lane_mask)
         if self.locomotion is not None:
             self.locomotion.reset(lane_mask)
+        if self.support is not None:
+            self.support.reset(lane_mask)
         if self.trajectory is not None:
             self._query_trajectory(lane_mask)
         if self.foot_poses is not None:
@@ -835,6 +855,8 @@ class WalkerVecEnv(VecJiminyEnv):
                 self.frames.refresh_average(self.step_dt)
         if self.locomotion is not None:
             self.locomotion.refresh()
+        if self.support is not None:
+            self.support.refresh()
         if self.trajectory is not None:
             self._query_trajectory(None, step=True)
         if self.foot_poses is not None:
@@ -928,6 +950,8 @@ class WalkerVecEnv(VecJiminyEnv):
         for term in ("base_height", "odometry_velocity", "capture_point", "joint_positions"):
             if term in self.reward_mixture:
                 total += self.reward_mixture[term] * self.tracking_rewards.reward(term)
+        if "robustness" in self.reward_mixture:
+            total += self.reward_mixture["robustness"] * self.support.reward_robustness
         return total
 
 
