@@ -232,6 +232,34 @@ class SupportIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in SUPPORT_IO_FIELDS]
 
 
+COMPOSE_DESC_INTS = ("source_kind", "source_rows", "node_kind", "node_terminal", "node_normalized", "node_slot", "node_row",
+                     "node_child_start", "node_child_count", "child", "cond_elem_start", "cond_elem_count", "cond_flags", "elem_slot",
+                     "elem_row", "elem_bounds")
+COMPOSE_DESC_DOUBLES = ("node_order", "child_weight", "cond_grace", "elem_low", "elem_high")
+
+
+class ComposeDesc(C.Structure):
+    """jm_compose_desc: the plan of the composition layer (jiminy_amd.compositions builds it)."""
+    _fields_ = [
+        ("n_sources", C.c_int32), ("source_kind", _pi), ("source_rows", _pi),
+        ("n_nodes", C.c_int32), ("node_kind", _pi), ("node_terminal", _pi), ("node_normalized", _pi), ("node_slot", _pi),
+        ("node_row", _pi), ("node_child_start", _pi), ("node_child_count", _pi), ("node_order", _pd),
+        ("n_children", C.c_int32), ("child", _pi), ("child_weight", _pd),
+        ("n_conditions", C.c_int32), ("cond_elem_start", _pi), ("cond_elem_count", _pi), ("cond_flags", _pi), ("cond_grace", _pd),
+        ("n_elements", C.c_int32), ("elem_slot", _pi), ("elem_row", _pi), ("elem_bounds", _pi), ("elem_low", _pd), ("elem_high", _pd),
+    ]
+
+
+COMPOSE_MAX_SOURCES = 16
+COMPOSE_IO_FIELDS = ("source", "time", "base_terminated", "base_truncated", "lane_mask", "reward", "node_value", "terminated",
+                     "truncated", "trigger", "violations")
+
+
+class ComposeIO(C.Structure):
+    """jm_compose_io: the device pointers of one launch of jm_block_compose; `source` is the table of slot base pointers."""
+    _fields_ = [("source", C.c_void_p * COMPOSE_MAX_SOURCES)] + [(name, C.c_void_p) for name in COMPOSE_IO_FIELDS[1:]]
+
+
 class CentroidalDesc(C.Structure):
     """jm_centroidal_desc: the plan of the centroidal quantities of a state (jiminy_amd.centroidal builds it)."""
     _fields_ = [

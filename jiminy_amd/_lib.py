@@ -62,6 +62,7 @@ ABI_SYMBOLS = (
     "jm_centroidal_plan_create", "jm_centroidal_plan_destroy", "jm_block_centroidal_state",
     "jm_trackrewards_plan_create", "jm_trackrewards_plan_destroy", "jm_block_tracking_rewards",
     "jm_support_plan_create", "jm_support_plan_destroy", "jm_block_support_polygon",
+    "jm_compose_plan_create", "jm_compose_plan_destroy", "jm_block_compose",
 )
 
 
@@ -154,6 +155,9 @@ class HipLibrary:
         L.jm_support_plan_create.argtypes = [C.POINTER(_abi.SupportDesc), C.POINTER(vp)]
         L.jm_support_plan_destroy.argtypes = [vp]
         L.jm_block_support_polygon.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.SupportIO), C.c_double, C.c_double, vp]
+        L.jm_compose_plan_create.argtypes = [C.POINTER(_abi.ComposeDesc), C.POINTER(vp)]
+        L.jm_compose_plan_destroy.argtypes = [vp]
+        L.jm_block_compose.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.ComposeIO), C.c_int32, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

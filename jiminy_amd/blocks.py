@@ -70,7 +70,7 @@ driven by a plan that jiminy_amd/support.py builds; specification: tests/golden/
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -1806,6 +1806,95 @@ class TrackingRewards:
         if plan:
             try:
                 self._L.jm_trackrewards_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+class Composition:
+    """The composition layer of the reference's environments per lane ≙ `ComposedJiminyEnv(reward=..., terminations=[...])`
+    (bases/pipeline.py:751-829 over bases/compositions.py, compositions/mixin.py, compositions/generic.py): `reward` is a
+    description of `jiminy_amd.compositions` (`RewardTerm`, `SurviveReward`, `AdditiveMixtureReward`,
+    `MultiplicativeMixtureReward`) or None, `terminations` a sequence of `compositions.Termination`, in evaluation order;
+    their rows are views of tensors other blocks of `engine` own, which must keep their identity.
+
+    `refresh(time, base_terminated, base_truncated, training=True, lane_mask=None)`: `time` `[B]` (engine dtype) is the
+    episode time of every lane, the two flags (bool or uint8 `[B]`) are those of the environment below.  Outputs: `terminated`,
+    `truncated` (uint8 `[B]`; a lane with a base flag keeps both and evaluates no condition), `trigger` (int32 `[B]`: the
+    first condition that fired, -1 for none or a base flag), `reward` `[B]`, `node_value` `[n_nodes][B]` (NaN where a node was
+    not evaluated; `info()` gives its rows by name, `node_names` their order) and `violations` (int32 `[B]`: the bit of the
+    first node advertised as normalised that left [0, 1], where the reference raises ValueError).  See
+    `jiminy_amd.compositions` for the three behaviours of the reference that hold here.
+
+    One launch on the engine's stream, without allocation, copy or synchronisation; lanes outside `lane_mask` keep every
+    tensor bit for bit.  The tensors never change identity."""
+
+    def __init__(self, engine, reward=None, terminations=()) -> None:
+        import ctypes as C
+        import os
+
+        from . import _abi, compositions
+        if os.environ.get("JIMINY_AMD_TENSOR_BLOCKS", "0") == "1":
+            raise NotImplementedError("the composition layer has no tensor-program form (JIMINY_AMD_TENSOR_BLOCKS=1): "
+                                      "it exists as the HIP kernel only")
+        self.plan = compositions.build_plan(reward, terminations, engine.batch_size, engine.dtype)
+        for t in self.plan.sources:
+            if t.device != engine.device:
+                raise ValueError("pipeline block tensors must be on the engine's device")
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self.node_names, self.condition_names = list(self.plan.node_names), list(self.plan.condition_names)
+        B = engine.batch_size
+        new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
+        self.reward, self.node_value = new(), new(self.plan.n_nodes)
+        self.terminated, self.truncated = new(dtype=torch.uint8), new(dtype=torch.uint8)
+        self.trigger, self.violations = new(dtype=torch.int32), new(dtype=torch.int32)
+        self.trigger.fill_(-1)
+        self._io = _abi.ComposeIO()
+        for s, ptr in enumerate(self.plan.source_ptr):
+            self._io.source[s] = ptr
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_compose_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    def info(self) -> Dict[str, torch.Tensor]:
+        """≙ the reward's entries of the reference's `info`: the row of `node_value` of every node by name (NaN on the lanes
+        where the node was not evaluated)."""
+        return {name: self.node_value[n] for n, name in enumerate(self.node_names)}
+
+    def refresh(self, time: torch.Tensor, base_terminated: Optional[torch.Tensor] = None, base_truncated: Optional[torch.Tensor] = None,
+                training: bool = True, lane_mask: Optional[torch.Tensor] = None) -> None:
+        eng, io, B = self._eng, self._io, self._eng.batch_size
+
+        def flags(t: Optional[torch.Tensor], name: str):
+            if t is None:
+                return None
+            if t.dtype == torch.bool:
+                t = t.view(torch.uint8)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != eng.device or tuple(t.shape) != (B,):
+                raise ValueError(f"{name} must be a contiguous bool or uint8 tensor of shape ({B},) on the engine's device")
+            return t
+        if time is not None:
+            _check_block_tensor(eng, time)
+            if tuple(time.shape) != (B,):
+                raise ValueError(f"time must have shape ({B},)")
+        held = [flags(base_terminated, "base_terminated"), flags(base_truncated, "base_truncated"), flags(lane_mask, "lane_mask")]
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        io.time, io.base_terminated, io.base_truncated, io.lane_mask = ptr(time), ptr(held[0]), ptr(held[1]), ptr(held[2])
+        io.reward, io.node_value = self.reward.data_ptr(), self.node_value.data_ptr() if self.plan.n_nodes else None
+        io.terminated, io.truncated = self.terminated.data_ptr(), self.truncated.data_ptr()
+        io.trigger, io.violations = self.trigger.data_ptr(), self.violations.data_ptr()
+        self._check(self._L.jm_block_compose(self._plan, self._dtype, B, self._C.byref(io), int(bool(training)), eng._stream()))
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_compose_plan_destroy(plan)
             except Exception:       # noqa: BLE001  (interpreter shutdown)
                 pass
 

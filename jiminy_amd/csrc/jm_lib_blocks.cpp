@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state, of the tracking rewards and of the support polygon, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state, of the tracking rewards, of the support polygon and of the composition layer, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "jm_centroidal.h"
 #include "jm_trackrewards.h"
 #include "jm_support.h"
+#include "jm_compose.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -145,6 +146,12 @@ struct jm_trackrewards_plan
 
 // the projected support polygon (jm_support.h)
 struct jm_support_plan
+{
+    DevicePlan dev;
+};
+
+// the composition layer (jm_compose.h)
+struct jm_compose_plan
 {
     DevicePlan dev;
 };
@@ -643,6 +650,35 @@ int32_t jm_block_support_polygon(const jm_support_plan * p, int32_t dtype, int64
         const jm::SupportIO<T> a{(const T *)io->pose, (const T *)io->odom_pose, (const T *)io->zmp, io->lane_mask, io->n_vertices,
                                  io->vertex_index, (T *)io->vertices, (T *)io->center, (T *)io->scalars};
         hipLaunchKernelGGL((jm::k_support_polygon<T>), grid, dim3(256), 0, s, it, a, cutoff_inner, cutoff_outer, (long long)B);
+    });
+}
+
+int32_t jm_compose_plan_create(const jm_compose_desc * desc, jm_compose_plan ** out)
+{
+    return plan_create("jm_compose_plan_create", desc, out, jm::compose_pack);
+}
+
+int32_t jm_compose_plan_destroy(jm_compose_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+int32_t jm_block_compose(const jm_compose_plan * p, int32_t dtype, int64_t B, const jm_compose_io * io, int32_t training, void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_compose: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_compose: bad sizes");
+    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_compose: bad dtype");
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
+        using T = decltype(z);
+        jm::ComposeIO<T> a;
+        for (int k = 0; k < jm::CMP_MAX_SOURCES; ++k) a.source[k] = io->source[k];
+        a.time = (const T *)io->time; a.base_terminated = io->base_terminated; a.base_truncated = io->base_truncated;
+        a.lane_mask = io->lane_mask; a.reward = (T *)io->reward; a.node_value = (T *)io->node_value;
+        a.terminated = io->terminated; a.truncated = io->truncated; a.trigger = io->trigger; a.violations = io->violations;
+        hipLaunchKernelGGL((jm::k_compose<T>), grid, dim3(256), 0, s, it, dt, a, (int)(training != 0), (long long)B);
     });
 }
 
