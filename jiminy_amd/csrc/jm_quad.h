@@ -40,10 +40,13 @@
 // stands at the head of the output pass: a load still pending there (spill reloads of the single evaluation of `start` /
 // `reset` / `refresh`, the status read-back of `refresh`) otherwise gets the compiler's own wait somewhere between the
 // output stores, on every path, and that wait also waits for every store issued before it.
+// JM_SCHED_FENCE: the instruction scheduler moves nothing across this point (the loads issued in front of it stay there).
 #ifdef JM_HOST_EMU
 #define JM_OUTPUT_PASS_BEGIN() ((void)0)
 #define JM_WAIT_VMEM() ((void)0)
+#define JM_SCHED_FENCE() ((void)0)
 #else
+#define JM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define JM_OUTPUT_PASS_BEGIN() asm volatile("; quad output pass" ::: "memory")
 // (gfx9 encoding of the s_waitcnt immediate, which gfx950 uses: vmcnt = bits 3:0 and 15:14 -> 0, expcnt = bits 6:4 -> 7 and
 // lgkmcnt = bits 11:8 -> 15, i.e. "do not wait" for the last two; the libraries are built for gfx950 only)
@@ -1820,8 +1823,11 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
     });
     cmdb[0] = T(0);
     static_for<1, NT>([&](auto tc) { cmdb[decltype(tc)::value] = A.command[(unsigned)Tp::trunk_motor[decltype(tc)::value] * B32 + r32]; });
-    static_for<0, N>([&](auto sc) { S.putl(R::CMDL + decltype(sc)::value, cmdl[decltype(sc)::value]); });
-    static_for<0, NT>([&](auto tc) { S.putb(R::CMDB + decltype(tc)::value, cmdb[decltype(tc)::value]); });
+    // (their stage-buffer rows are written below, behind the state loads: see the launch prologue there)
+    auto put_commands = [&] {
+        static_for<0, N>([&](auto sc) { S.putl(R::CMDL + decltype(sc)::value, cmdl[decltype(sc)::value]); });
+        static_for<0, NT>([&](auto tc) { S.putb(R::CMDB + decltype(tc)::value, cmdb[decltype(tc)::value]); });
+    };
 
     // every mode runs through the same evaluation loop (two inlined copies of the dynamics: with
     // and without the output code): `start`, `reset` and `dynamics` are one evaluation at a given
@@ -1872,32 +1878,50 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
     if constexpr (PH != 0) split_e = C->split_e;
     if (PH == 0 || (PH == 1 && split_e == 0))
     {
-        bool bad = false;
+        // Launch prologue: EVERY global load of the state (and, above, of the commands) is issued before the first
+        // stage-buffer store.  A store needs its datum, so a load followed by its own store is a wait for that one load --
+        // written row by row, the prologue was some twenty memory round trips in a row per wave, at a moment when the
+        // partner wave of the SIMD sits in the same prologue and covers none of them.  Now it is one.
+        T xq[NQB], xv[NVB], xa[NVB], lq[N], lv[N], la[N];
         static_for<0, NQB>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
-            const unsigned o = (unsigned)I::qrow(i) * B32 + r32;
-            const T x = qsrc[o];
-            S.putb(R::Q0B + i, x); bad |= (x != x);
-            if (A.mode == MODE_RESET && lead) A.q[o] = x;
+            xq[i] = qsrc[(unsigned)I::qrow(i) * B32 + r32];
         });
         static_for<0, NVB>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const unsigned o = (unsigned)I::vrow(i) * B32 + r32;
-            const T x = vsrc[o], y = stepping ? A.a[o] : T(0);
-            S.putb(R::V0B + i, x); S.putb(R::KVB + i, x); S.putb(R::ACCVB + i, T(0)); S.putb(R::ACCAB + i, T(0));
-            ddqb[i] = y;
-            bad |= (x != x) || (y != y);
-            if (A.mode == MODE_RESET && lead) A.v[o] = x;
+            xv[i] = vsrc[o]; xa[i] = stepping ? A.a[o] : T(0);
         });
         static_for<0, N>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            T x = T(0), y = T(0), z = T(0);
+            lq[s] = T(0); lv[s] = T(0); la[s] = T(0);
             if (ix.has[s])
             {
                 const unsigned oq = (unsigned)ix.rq[s] * B32 + r32, ov = (unsigned)ix.rv[s] * B32 + r32;
-                x = qsrc[oq]; y = vsrc[ov]; z = stepping ? A.a[ov] : T(0);
-                if (A.mode == MODE_RESET) { A.q[oq] = x; A.v[ov] = y; }
+                lq[s] = qsrc[oq]; lv[s] = vsrc[ov]; la[s] = stepping ? A.a[ov] : T(0);
             }
+        });
+        JM_SCHED_FENCE();
+        put_commands();
+        bool bad = false;
+        static_for<0, NQB>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const T x = xq[i];
+            S.putb(R::Q0B + i, x); bad |= (x != x);
+            if (A.mode == MODE_RESET && lead) A.q[(unsigned)I::qrow(i) * B32 + r32] = x;
+        });
+        static_for<0, NVB>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const T x = xv[i], y = xa[i];
+            S.putb(R::V0B + i, x); S.putb(R::KVB + i, x); S.putb(R::ACCVB + i, T(0)); S.putb(R::ACCAB + i, T(0));
+            ddqb[i] = y;
+            bad |= (x != x) || (y != y);
+            if (A.mode == MODE_RESET && lead) A.v[(unsigned)I::vrow(i) * B32 + r32] = x;
+        });
+        static_for<0, N>([&](auto sc) {
+            constexpr int s = decltype(sc)::value;
+            const T x = lq[s], y = lv[s], z = la[s];
+            if (ix.has[s] && A.mode == MODE_RESET) { A.q[(unsigned)ix.rq[s] * B32 + r32] = x; A.v[(unsigned)ix.rv[s] * B32 + r32] = y; }
             S.putl(R::Q0L + s, x); S.putl(R::V0L + s, y); S.putl(R::KVL + s, y); S.putl(R::ACCVL + s, T(0)); S.putl(R::ACCAL + s, T(0));
             ddq[s] = z;
             bad |= (x != x) || (y != y) || (z != z);
@@ -1909,6 +1933,7 @@ JM_DEV void quad_lane_run(const BatchArgs<T> & A, long long r, int k, const T * 
     }
     else
     {
+        put_commands();
         // split stepping: what the previous launch left in the stage buffer
         status = (int)S.getl(SR::STATUSL);
         if constexpr (PH == 1)
@@ -2227,6 +2252,31 @@ struct DppQuad
     static __device__ __forceinline__ void table_ready() { __syncthreads(); }
 };
 
+// Copy of the limb table into LDS by the NTH threads of a block, four elements per thread in flight: the loads of a
+// chunk are all issued before its first LDS store (a load followed by its own store is one memory round trip per element;
+// the ANYmal table is one chunk of a 256-thread block).  Out-of-range elements of the last chunk load the last entry.
+template<class T, int NTAB, int NTH> static __device__ __forceinline__ void stage_limb_table(T * table, const T * src, int tid)
+{
+    constexpr int U = 4;
+#pragma nounroll
+    for (int base = tid; base < NTAB; base += U * NTH)
+    {
+        T x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+        {
+            const int i = base + u * NTH;
+            x[u] = src[i < NTAB ? i : NTAB - 1];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+        {
+            const int i = base + u * NTH;
+            if (i < NTAB) table[i] = x[u];
+        }
+    }
+}
+
 // waves per block: they share one copy of the limb table. Pick the block size that keeps the most
 // waves resident per CU under the 160 KiB of LDS (a CU runs at most 2 such waves per SIMD).
 template<class T, class Tp> constexpr int quad_block_waves()
@@ -2268,8 +2318,7 @@ k_quad(const BatchArgs<T> A)
     __shared__ T table[Q::TABLE];
     __shared__ T stage_l[QRows<Tp>::NL * NTH];
     __shared__ T stage_b[QRows<Tp>::NB * (NTH / 4)];
-#pragma nounroll
-    for (int i = threadIdx.x; i < Q::TABLE; i += NTH) table[i] = A.P[Q::OFFSET + i];
+    stage_limb_table<T, Q::TABLE, NTH>(table, A.P + Q::OFFSET, (int)threadIdx.x);
     const long long r = (long long)blockIdx.x * (NTH / 4) + (threadIdx.x >> 2);
     const int k = threadIdx.x & 3;
     // early exits are whole quads; waves that still run meet at the barrier inside quad_lane_run
@@ -2289,8 +2338,7 @@ k_quad_gen(const BatchArgs<T> A)
     __shared__ T table[Q::TABLE];
     __shared__ T stage_l[QRows<Tp>::NL * NTH];
     __shared__ T stage_b[QRows<Tp>::NB * (NTH / 4)];
-#pragma nounroll
-    for (int i = threadIdx.x; i < Q::TABLE; i += NTH) table[i] = A.P[Q::OFFSET + i];
+    stage_limb_table<T, Q::TABLE, NTH>(table, A.P + Q::OFFSET, (int)threadIdx.x);
     const long long r = (long long)blockIdx.x * (NTH / 4) + (threadIdx.x >> 2);
     const int k = threadIdx.x & 3;
     if (r >= A.B) return;
