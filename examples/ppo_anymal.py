@@ -128,11 +128,18 @@ class PPO:
 
 
 def flatten_anymal_obs(obs: Dict[str, Any]) -> torch.Tensor:
-    """Device-side feature vector: joint positions / all velocities, IMU, Mahony quaternion, PD targets."""
+    """The feature vector below as a tensor program (what `main` did before `AssembleObservation`; kept for comparison)."""
     q, v = obs["states"]["agent"]["q"], obs["states"]["agent"]["v"]
     parts = [q[:, 7:], v, obs["measurements"]["ImuSensor"].flatten(1), obs["features"]["mahony_filter"].flatten(1),
              obs["actions"]["pd_controller"].flatten(1)]
     return torch.cat(parts, dim=1).float()
+
+
+# the feature vector of the policy: joint positions, all velocities, IMU, Mahony quaternion, PD targets -- the leaves sorted by
+# these keys are in the order of the list
+ANYMAL_OBS_LAYOUT = [(("0_q",), ("states", "agent", "q", [(7, None)])), (("1_v",), ("states", "agent", "v")),
+                     (("2_imu",), ("measurements", "ImuSensor")), (("3_mahony",), ("features", "mahony_filter")),
+                     (("4_targets",), ("actions", "pd_controller"))]
 
 
 def main() -> None:
@@ -157,15 +164,17 @@ def main() -> None:
         dist.init_process_group("nccl")     # RCCL
     rank = dist.get_rank() if world > 1 else 0
     from jiminy_amd.envs import make_anymal_env
+    from jiminy_amd.wrappers import AssembleObservation
     std_ratio = {k: v for k, v in (("ground", args.std_ratio_ground), ("sensors", args.std_ratio_sensors)) if v > 0}
-    env = make_anymal_env(args.envs, device=dev, contact_model=args.contact_model, std_ratio=std_ratio or None)
-    obs_d, _ = env.reset(seed=rank)
-    obs = flatten_anymal_obs(obs_d)
+    # one launch per step assembles the (B, W) float32 tensor the policy reads (the rollout buffer copies it)
+    env = AssembleObservation(make_anymal_env(args.envs, device=dev, contact_model=args.contact_model, std_ratio=std_ratio or None),
+                              layout=ANYMAL_OBS_LAYOUT, dtype=torch.float32)
+    obs, _ = env.reset(seed=rank)
     ppo = PPO(obs.shape[1], env.model.nmotors, dev, epochs=args.epochs, minibatches=args.minibatches)
 
     def env_step(action: torch.Tensor):
         o, r, term, trunc, _ = env.step(0.25 * torch.tanh(action).double())
-        return flatten_anymal_obs(o), r.float(), term | trunc
+        return o, r.float(), term | trunc
     hist = []
     t_roll = t_upd = 0.0
     for it in range(args.iters + 1):          # iteration 0 = warm-up, not timed

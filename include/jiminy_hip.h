@@ -1321,6 +1321,60 @@ int32_t jm_compose_plan_destroy(jm_compose_plan * plan);
 int32_t jm_block_compose(const jm_compose_plan * plan, int32_t dtype, int64_t batch_size, const jm_compose_io * io, int32_t training,
                          void * stream);
 
+/* ---- Observation assembly: `FlattenObservation(StackObservation(NormalizeObservation(ScaleObservation(
+ * AdaptLayoutObservation(env)))))` as one launch, from the rows other blocks left on the device to the `(B, W)` tensor the learner
+ * reads; batched, one lane = one environment, independent of the topology.  New symbols only: no existing structure or signature
+ * changed with them.  Reference (python/gym_jiminy/common/gym_jiminy/common/wrappers): observation_layout.py:36-311, :314-443,
+ * :446-540 (`_adapt_layout`, `AdaptLayoutObservation`, `FilterObservation`), scale.py:31-84, :141-244 (`_array_scale`,
+ * `ScaleObservation`), normalize.py:49-114 (`NormalizeObservation`), observation_stack.py:40-265 (`StackObservation`), flatten.py
+ * (`FlattenObservation`).
+ * jm_observe_desc: the plan (host arrays, copied by jm_observe_plan_create, which validates them: JM_EINVAL + jm_last_error before
+ *   any device call).
+ *   Sources, 1 to 16: slot s is the base pointer `source[s]` of the launch, an array `[source_rows[s]][B]` of the input type.
+ *   Elements, 1 to 2048 (D): one scalar of one kept leaf.  Element e reads (`elem_slot`, `elem_row`), is multiplied by the
+ *     `elem_mult_count[e]` (at most 4) factors `multiplier[elem_mult_start[e] ..]` one after the other, each product rounded,
+ *     and becomes `(x - elem_mean[e]) / elem_scale[e]` (0 and 1 where the leaf is not normalised; a zero scale is refused).
+ *   `num_stack`, 1 to 16.  Positions, 1 to 8192 (W): column p of the output holds element `pos_elem[p]` at age `pos_age[p]`
+ *     (0: the current frame).  An element is emitted once at age 0 (not stacked) or once at every age (stacked).
+ * jm_observe_io: the device pointers of one launch.  `source[16]`; `reset_mask` (uint8 `[B]`, NULL: none): lanes whose older
+ *   frames restart from zero; `hist` `[num_stack][D][B]` of the input type, owned by the caller, zero at creation (the rows of
+ *   an element that is not stacked are never touched); `out` `[B][W]` of the output type, which may alias neither a source nor
+ *   the history (JM_EINVAL).
+ * jm_block_observe: `shift` != 0 moves every frame one age up before the current frame is written (`skip_frames_ratio` of the
+ *   reference skips that on some steps: the current frame is then overwritten in place).  (dtype_in, dtype_out) is float64 ->
+ *   float64, float64 -> float32 or float32 -> float32; the cast is the last operation.  Nothing is allocated, copied or
+ *   synchronised. */
+typedef struct jm_observe_desc
+{
+    int32_t n_sources;
+    const int32_t * source_rows;        /* [n_sources] */
+    int32_t n_elements;
+    const int32_t * elem_slot;          /* [n_elements] */
+    const int32_t * elem_row;           /* [n_elements] */
+    const int32_t * elem_mult_start;    /* [n_elements] */
+    const int32_t * elem_mult_count;    /* [n_elements] */
+    const double * elem_mean;           /* [n_elements] */
+    const double * elem_scale;          /* [n_elements] */
+    int32_t n_multipliers;
+    const double * multiplier;          /* [n_multipliers] */
+    int32_t num_stack;
+    int32_t n_positions;
+    const int32_t * pos_elem;           /* [n_positions] */
+    const int32_t * pos_age;            /* [n_positions] */
+} jm_observe_desc;
+typedef struct jm_observe_io
+{
+    const void * source[16];
+    const uint8_t * reset_mask;
+    void * hist;
+    void * out;
+} jm_observe_io;
+typedef struct jm_observe_plan jm_observe_plan;
+int32_t jm_observe_plan_create(const jm_observe_desc * desc, jm_observe_plan ** out);
+int32_t jm_observe_plan_destroy(jm_observe_plan * plan);
+int32_t jm_block_observe(const jm_observe_plan * plan, int32_t dtype_in, int32_t dtype_out, int64_t batch_size, const jm_observe_io * io,
+                         int32_t shift, void * stream);
+
 /* Copy the message of the last error raised on the calling thread. */
 int32_t jm_last_error(char * buffer, size_t size);
 

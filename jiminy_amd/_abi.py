@@ -260,6 +260,31 @@ class ComposeIO(C.Structure):
     _fields_ = [("source", C.c_void_p * COMPOSE_MAX_SOURCES)] + [(name, C.c_void_p) for name in COMPOSE_IO_FIELDS[1:]]
 
 
+OBSERVE_DESC_INTS = ("source_rows", "elem_slot", "elem_row", "elem_mult_start", "elem_mult_count", "pos_elem", "pos_age")
+OBSERVE_DESC_DOUBLES = ("elem_mean", "elem_scale", "multiplier")
+
+
+class ObserveDesc(C.Structure):
+    """jm_observe_desc: the plan of the observation assembly (jiminy_amd.observe builds it)."""
+    _fields_ = [
+        ("n_sources", C.c_int32), ("source_rows", _pi),
+        ("n_elements", C.c_int32), ("elem_slot", _pi), ("elem_row", _pi), ("elem_mult_start", _pi), ("elem_mult_count", _pi),
+        ("elem_mean", _pd), ("elem_scale", _pd),
+        ("n_multipliers", C.c_int32), ("multiplier", _pd),
+        ("num_stack", C.c_int32),
+        ("n_positions", C.c_int32), ("pos_elem", _pi), ("pos_age", _pi),
+    ]
+
+
+OBSERVE_MAX_SOURCES = 16
+OBSERVE_IO_FIELDS = ("source", "reset_mask", "hist", "out")
+
+
+class ObserveIO(C.Structure):
+    """jm_observe_io: the device pointers of one launch of jm_block_observe; `source` is the table of slot base pointers."""
+    _fields_ = [("source", C.c_void_p * OBSERVE_MAX_SOURCES)] + [(name, C.c_void_p) for name in OBSERVE_IO_FIELDS[1:]]
+
+
 class CentroidalDesc(C.Structure):
     """jm_centroidal_desc: the plan of the centroidal quantities of a state (jiminy_amd.centroidal builds it)."""
     _fields_ = [

@@ -63,6 +63,7 @@ ABI_SYMBOLS = (
     "jm_trackrewards_plan_create", "jm_trackrewards_plan_destroy", "jm_block_tracking_rewards",
     "jm_support_plan_create", "jm_support_plan_destroy", "jm_block_support_polygon",
     "jm_compose_plan_create", "jm_compose_plan_destroy", "jm_block_compose",
+    "jm_observe_plan_create", "jm_observe_plan_destroy", "jm_block_observe",
 )
 
 
@@ -158,6 +159,9 @@ class HipLibrary:
         L.jm_compose_plan_create.argtypes = [C.POINTER(_abi.ComposeDesc), C.POINTER(vp)]
         L.jm_compose_plan_destroy.argtypes = [vp]
         L.jm_block_compose.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.ComposeIO), C.c_int32, vp]
+        L.jm_observe_plan_create.argtypes = [C.POINTER(_abi.ObserveDesc), C.POINTER(vp)]
+        L.jm_observe_plan_destroy.argtypes = [vp]
+        L.jm_block_observe.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(_abi.ObserveIO), C.c_int32, vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

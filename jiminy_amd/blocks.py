@@ -1899,6 +1899,82 @@ class Composition:
                 pass
 
 
+class ObservationAssembler:
+    """The observation the learner reads, assembled per lane ≙ `FlattenObservation(StackObservation(NormalizeObservation(
+    ScaleObservation(AdaptLayoutObservation(env)))))` (wrappers/observation_layout.py:36-540, scale.py:31-244, normalize.py:49-114,
+    observation_stack.py:40-265, flatten.py) as one launch of `jm_block_observe` (csrc/jm_observe.h).  `obs` is the nested
+    observation of the environment, whose leaves are batch-first views of `[rows][B]` tensors other blocks of `engine` own; the
+    other arguments are those of the wrappers (`jiminy_amd.observe.build_plan`).
+
+    `out` `(B, W)` in `dtype` and `hist` `[num_stack][D][B]` in the engine dtype are the block's own and never change identity.
+    `refresh(shift=True, reset_mask=None, obs=None)`: one launch on the engine's stream, without allocation, copy or
+    synchronisation; `shift=False` overwrites the current frame only (`skip_frames_ratio`), `reset_mask` (bool or uint8 `[B]`)
+    restarts the older frames of those lanes from zero, `obs` is a new observation of the same environment whose leaves are
+    read instead (the data pointers are read at every launch either way).  `reset(lane_mask=None)` zeroes the history."""
+
+    def __init__(self, engine, obs, **spec) -> None:
+        import ctypes as C
+        import os
+
+        from . import _abi, observe
+        if os.environ.get("JIMINY_AMD_TENSOR_BLOCKS", "0") == "1":
+            raise NotImplementedError("the observation assembly has no tensor-program form of its own (JIMINY_AMD_TENSOR_BLOCKS=1): "
+                                      "wrappers.AssembleObservation runs the chain of tensor wrappers instead")
+        self.plan = observe.build_plan(obs, engine_dtype=engine.dtype, **spec)
+        self._leaves = observe.source_tensors(obs, self.plan)
+        for t in self._leaves:
+            if t.device != engine.device:
+                raise ValueError("pipeline block tensors must be on the engine's device")
+        self._C, self._observe = C, observe
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        code = lambda dt: _abi.JM_F64 if dt == torch.float64 else _abi.JM_F32      # noqa: E731
+        self._dtype_in, self._dtype_out = code(self.plan.dtype_in), code(self.plan.dtype_out)
+        B = engine.batch_size
+        self.hist = torch.zeros((self.plan.num_stack, self.plan.n_elements, B), dtype=engine.dtype, device=engine.device)
+        self.out = torch.zeros((B, self.plan.n_positions), dtype=self.plan.dtype_out, device=engine.device)
+        observe.check_no_alias(self.out, [(f"observation leaf {p}", t) for p, t in zip(self.plan.source_paths, self._leaves)])
+        self._io = _abi.ObserveIO()
+        self._io.hist, self._io.out = self.hist.data_ptr(), self.out.data_ptr()
+        desc, keep = self.plan.desc()
+        self._plan = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            self._check(self._L.jm_observe_plan_create(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
+        if lane_mask is None:
+            self.hist.zero_()
+        else:
+            self.hist.masked_fill_(lane_mask.to(torch.bool), 0)
+
+    def refresh(self, shift: bool = True, reset_mask: Optional[torch.Tensor] = None, obs=None) -> None:
+        eng, io, B = self._eng, self._io, self._eng.batch_size
+        leaves = self._leaves if obs is None else self._observe.source_tensors(obs, self.plan)
+        for s, (t, first) in enumerate(zip(leaves, self._leaves)):
+            if t is not first and (t.shape != first.shape or t.stride() != first.stride() or t.dtype != first.dtype or t.device != first.device):
+                raise ValueError(f"observation leaf {self.plan.source_paths[s]} changed its shape, strides, dtype or device")
+            io.source[s] = t.data_ptr()
+        if reset_mask is not None:
+            if reset_mask.dtype == torch.bool:
+                reset_mask = reset_mask.view(torch.uint8)
+            if reset_mask.dtype != torch.uint8 or not reset_mask.is_contiguous() or reset_mask.device != eng.device or \
+                    tuple(reset_mask.shape) != (B,):
+                raise ValueError(f"reset_mask must be a contiguous bool or uint8 tensor of shape ({B},) on the engine's device")
+        io.reset_mask = None if reset_mask is None else reset_mask.data_ptr()
+        self._check(self._L.jm_block_observe(self._plan, self._dtype_in, self._dtype_out, B, self._C.byref(io), int(bool(shift)),
+                                             eng._stream()))
+
+    def __del__(self) -> None:
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                self._L.jm_observe_plan_destroy(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
 def pd_controller(encoder_data: torch.Tensor, command_state: torch.Tensor,
                   command_state_lower: torch.Tensor, command_state_upper: torch.Tensor,
                   kp: torch.Tensor, kd: torch.Tensor, motors_effort_limit: torch.Tensor,

@@ -348,7 +348,7 @@ def write_header(model: CompiledModel) -> str:
 
 def _sources() -> List[str]:
     return [os.path.join(CSRC, n) for n in ("jm_lib.cpp", "jm_kernels.h", "jm_math.h", "jm_quad.h",
-                                            "jm_pack.h", "jm_adaptive.h", "jm_blocks.h", "jm_deform.h", "jm_attitude.h", "jm_frames.h", "jm_locomotion.h", "jm_actuation.h", "jm_footposes.h", "jm_tracking.h", "jm_trajectory.h", "jm_centroidal.h", "jm_trackrewards.h", "jm_support.h", "jm_compose.h", "jm_random.h",
+                                            "jm_pack.h", "jm_adaptive.h", "jm_blocks.h", "jm_deform.h", "jm_attitude.h", "jm_frames.h", "jm_locomotion.h", "jm_actuation.h", "jm_footposes.h", "jm_tracking.h", "jm_trajectory.h", "jm_centroidal.h", "jm_trackrewards.h", "jm_support.h", "jm_compose.h", "jm_observe.h", "jm_random.h",
                                             "jm_constraint.h", "jm_qcon.h", "jm_qtip.h", "jm_qdopri.h", "jm_lib_constraint.cpp",
                                             "jm_lib_blocks.cpp", "jm_rotation.h", "jm_error.h", "jm_ground.h")] + \
            [os.path.join(CSRC, "..", "..", "include", "jiminy_hip.h"), os.path.join(CSRC, "jm_dispatch.h")]

@@ -1,5 +1,5 @@
 // jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state, of the tracking rewards, of the support polygon and of the composition layer, and the seeding of the generators.  Compiled with the
+// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state, of the tracking rewards, of the support polygon, of the composition layer and of the observation assembly, and the seeding of the generators.  Compiled with the
 // flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
 // that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "jm_trackrewards.h"
 #include "jm_support.h"
 #include "jm_compose.h"
+#include "jm_observe.h"
 #include "jm_random.h"
 #include "jm_error.h"
 
@@ -154,6 +155,13 @@ struct jm_support_plan
 struct jm_compose_plan
 {
     DevicePlan dev;
+};
+
+// the observation assembly (jm_observe.h): the integer table stays on the host as well, for the aliasing check of a launch
+struct jm_observe_plan
+{
+    DevicePlan dev;
+    std::vector<int32_t> it;
 };
 
 extern "C"
@@ -680,6 +688,56 @@ int32_t jm_block_compose(const jm_compose_plan * p, int32_t dtype, int64_t B, co
         a.terminated = io->terminated; a.truncated = io->truncated; a.trigger = io->trigger; a.violations = io->violations;
         hipLaunchKernelGGL((jm::k_compose<T>), grid, dim3(256), 0, s, it, dt, a, (int)(training != 0), (long long)B);
     });
+}
+
+// ≙ the constructors of `AdaptLayoutObservation` (observation_layout.py:394-429), `ScaleObservation` (scale.py:150-229),
+// `NormalizeObservation` (normalize.py:49-90), `StackObservation` (observation_stack.py:40-160) and `FlattenObservation`
+// (flatten.py), whose result the caller states as elements and positions
+int32_t jm_observe_plan_create(const jm_observe_desc * desc, jm_observe_plan ** out)
+{
+    std::vector<int32_t> kept;
+    const int32_t rc = plan_create("jm_observe_plan_create", desc, out,
+                                   [&](const jm_observe_desc * d, std::vector<int32_t> & it, std::vector<double> & dt, std::string & why) {
+                                       const bool ok = jm::observe_pack(d, it, dt, why);
+                                       if (ok) kept = it;
+                                       return ok;
+                                   });
+    if (rc == JM_OK) (*out)->it = std::move(kept);
+    return rc;
+}
+
+int32_t jm_observe_plan_destroy(jm_observe_plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+// ≙ one `transform_observation` of the whole chain: `_array_scale` per scale operation (scale.py:236-244), the affine map of
+// normalize.py:92-114, the shift and the write of observation_stack.py:225-265 and the concatenation of flatten.py
+int32_t jm_block_observe(const jm_observe_plan * p, int32_t dtype_in, int32_t dtype_out, int64_t B, const jm_observe_io * io, int32_t shift,
+                         void * stream)
+{
+    if (!p || !io) return fail(JM_EINVAL, "jm_block_observe: null argument");
+    if (B <= 0) return fail(JM_EINVAL, "jm_block_observe: bad sizes");
+    std::string why;
+    if (!jm::observe_dtype_check(dtype_in, dtype_out, why)) return fail(JM_EINVAL, why);
+    if (!jm::observe_alias_check(p->it, io, B, dtype_in == JM_F64 ? 8 : 4, dtype_out == JM_F64 ? 8 : 4, why)) return fail(JM_EINVAL, why);
+    const int32_t * it = p->dev.it;
+    const double * dt = p->dev.dt;
+    const dim3 grid((unsigned)((B + jm::OBS_TILE - 1) / jm::OBS_TILE), (unsigned)((p->it[1] + jm::OBS_TILE - 1) / jm::OBS_TILE));
+    const auto launch = [&](auto zi, auto zo) {
+        using TIn = decltype(zi);
+        using TOut = decltype(zo);
+        jm::ObserveIO<TIn, TOut> a;
+        for (int k = 0; k < jm::OBS_MAX_SOURCES; ++k) a.source[k] = io->source[k];
+        a.reset_mask = io->reset_mask; a.hist = (TIn *)io->hist; a.out = (TOut *)io->out;
+        hipLaunchKernelGGL((jm::k_observe<TIn, TOut>), grid, dim3(256), 0, (hipStream_t)stream, it, dt, a, (int)(shift != 0), (long long)B);
+    };
+    if (dtype_in == JM_F64 && dtype_out == JM_F64) launch(double(), double());
+    else if (dtype_in == JM_F64) launch(double(), float());
+    else launch(float(), float());
+    HIP_TRY(hipGetLastError());
+    return JM_OK;
 }
 
 // ziggurat tables: computed once on the host (random.cc:66-96), one copy per device
