@@ -296,6 +296,17 @@ class CentroidalDesc(C.Structure):
     ]
 
 
+# The plan families of the plan-backed blocks: `jm_<family>_plan_create(const jm_<family>_desc *, jm_<family>_plan **)` and
+# `jm_<family>_plan_destroy(jm_<family>_plan *)`.  The loader declares both entry points of every family from this table,
+# and a block of jiminy_amd.blocks names its family when it creates its plan.
+PLAN_FAMILIES = {
+    "deform": DeformDesc, "attitude": AttitudeDesc, "frames": FramesDesc, "locomotion": LocomotionDesc,
+    "actuation": ActuationDesc, "footposes": FootPosesDesc, "tracking": TrackingDesc, "trajectory": TrajectoryDesc,
+    "centroidal": CentroidalDesc, "trackrewards": TrackRewardsDesc, "support": SupportDesc, "compose": ComposeDesc,
+    "observe": ObserveDesc,
+}
+
+
 class Options(C.Structure):
     _fields_ = [
         ("gravity", C.c_double * 6),

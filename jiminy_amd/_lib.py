@@ -37,7 +37,7 @@ _EXC = {
 
 _LIBS: Dict[Tuple[str, int], "HipLibrary"] = {}
 
-# every symbol include/jiminy_hip.h declares
+# every symbol include/jiminy_hip.h declares (the create / destroy pair of every plan family comes from _abi.PLAN_FAMILIES)
 ABI_SYMBOLS = (
     "jm_topology_signature", "jm_abi_version", "jm_model_create", "jm_model_destroy",
     "jm_batch_create", "jm_batch_destroy", "jm_batch_set_options", "jm_batch_workspace_rows",
@@ -49,22 +49,12 @@ ABI_SYMBOLS = (
     "jm_batch_set_constraint_options", "jm_batch_constraint_rows", "jm_block_sensor_delay",
     "jm_batch_set_ground", "jm_batch_set_applied_frames", "jm_batch_set_joint_locks", "jm_block_pd_adapter", "jm_block_motor_safety_limit",
     "jm_block_model_bias", "jm_engine_rng_seed",
-    "jm_deform_plan_create", "jm_deform_plan_destroy", "jm_block_deformation_estimator",
     "jm_batch_set_process_forces",
-    "jm_attitude_plan_create", "jm_attitude_plan_destroy", "jm_block_attitude_init", "jm_block_mahony_observer",
-    "jm_block_body_observer",
-    "jm_frames_plan_create", "jm_frames_plan_destroy", "jm_block_frame_kinematics", "jm_block_frame_average",
-    "jm_locomotion_plan_create", "jm_locomotion_plan_destroy", "jm_block_locomotion", "jm_block_locomotion_ground",
-    "jm_actuation_plan_create", "jm_actuation_plan_destroy", "jm_block_actuation",
-    "jm_footposes_plan_create", "jm_footposes_plan_destroy", "jm_block_foot_poses",
-    "jm_tracking_plan_create", "jm_tracking_plan_destroy", "jm_block_tracking",
-    "jm_trajectory_plan_create", "jm_trajectory_plan_destroy", "jm_block_trajectory_state",
-    "jm_centroidal_plan_create", "jm_centroidal_plan_destroy", "jm_block_centroidal_state",
-    "jm_trackrewards_plan_create", "jm_trackrewards_plan_destroy", "jm_block_tracking_rewards",
-    "jm_support_plan_create", "jm_support_plan_destroy", "jm_block_support_polygon",
-    "jm_compose_plan_create", "jm_compose_plan_destroy", "jm_block_compose",
-    "jm_observe_plan_create", "jm_observe_plan_destroy", "jm_block_observe",
-)
+    "jm_block_deformation_estimator", "jm_block_attitude_init", "jm_block_mahony_observer", "jm_block_body_observer",
+    "jm_block_frame_kinematics", "jm_block_frame_average", "jm_block_locomotion", "jm_block_locomotion_ground",
+    "jm_block_actuation", "jm_block_foot_poses", "jm_block_tracking", "jm_block_trajectory_state",
+    "jm_block_centroidal_state", "jm_block_tracking_rewards", "jm_block_support_polygon", "jm_block_compose", "jm_block_observe",
+) + tuple(f"jm_{family}_plan_{op}" for family in _abi.PLAN_FAMILIES for op in ("create", "destroy"))
 
 
 class HipLibrary:
@@ -116,52 +106,29 @@ class HipLibrary:
         L.jm_batch_set_applied_frames.argtypes = [vp, C.c_int32, dp, ip]
         L.jm_batch_set_joint_locks.argtypes = [vp, C.c_int32]
         L.jm_batch_set_process_forces.argtypes = [vp, C.c_int32, C.POINTER(_abi.ProcessForce)]
-        L.jm_deform_plan_create.argtypes = [C.POINTER(_abi.DeformDesc), C.POINTER(vp)]
-        L.jm_deform_plan_destroy.argtypes = [vp]
         L.jm_block_deformation_estimator.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp]
-        L.jm_attitude_plan_create.argtypes = [C.POINTER(_abi.AttitudeDesc), C.POINTER(vp)]
-        L.jm_attitude_plan_destroy.argtypes = [vp]
         L.jm_block_attitude_init.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
         L.jm_block_mahony_observer.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_double, C.c_int32, vp, vp]
         L.jm_block_body_observer.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_double,
                                              vp, vp]
-        L.jm_frames_plan_create.argtypes = [C.POINTER(_abi.FramesDesc), C.POINTER(vp)]
-        L.jm_frames_plan_destroy.argtypes = [vp]
         L.jm_block_frame_kinematics.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.jm_block_frame_average.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp]
-        L.jm_locomotion_plan_create.argtypes = [C.POINTER(_abi.LocomotionDesc), C.POINTER(vp)]
-        L.jm_locomotion_plan_destroy.argtypes = [vp]
         L.jm_block_locomotion.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.LocomotionIO), C.c_double, C.c_double, vp]
         L.jm_block_locomotion_ground.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.LocomotionIO),
                                                  C.POINTER(_abi.LocomotionGround), C.c_double, C.c_double, vp]
-        L.jm_actuation_plan_create.argtypes = [C.POINTER(_abi.ActuationDesc), C.POINTER(vp)]
-        L.jm_actuation_plan_destroy.argtypes = [vp]
         L.jm_block_actuation.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.ActuationIO), C.c_int32, C.c_int32, C.c_double,
                                          C.c_double, C.c_double, vp]
-        L.jm_footposes_plan_create.argtypes = [C.POINTER(_abi.FootPosesDesc), C.POINTER(vp)]
-        L.jm_footposes_plan_destroy.argtypes = [vp]
         L.jm_block_foot_poses.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.FootPosesIO), C.c_double, C.c_double, vp]
-        L.jm_tracking_plan_create.argtypes = [C.POINTER(_abi.TrackingDesc), C.POINTER(vp)]
-        L.jm_tracking_plan_destroy.argtypes = [vp]
         L.jm_block_tracking.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrackingIO), C.c_int32, C.c_double, vp]
-        L.jm_trajectory_plan_create.argtypes = [C.POINTER(_abi.TrajectoryDesc), C.POINTER(vp)]
-        L.jm_trajectory_plan_destroy.argtypes = [vp]
         L.jm_block_trajectory_state.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrajectoryIO), vp]
-        L.jm_centroidal_plan_create.argtypes = [C.POINTER(_abi.CentroidalDesc), C.POINTER(vp)]
-        L.jm_centroidal_plan_destroy.argtypes = [vp]
         L.jm_block_centroidal_state.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp]
-        L.jm_trackrewards_plan_create.argtypes = [C.POINTER(_abi.TrackRewardsDesc), C.POINTER(vp)]
-        L.jm_trackrewards_plan_destroy.argtypes = [vp]
         L.jm_block_tracking_rewards.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.TrackRewardsIO), dp, vp]
-        L.jm_support_plan_create.argtypes = [C.POINTER(_abi.SupportDesc), C.POINTER(vp)]
-        L.jm_support_plan_destroy.argtypes = [vp]
         L.jm_block_support_polygon.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.SupportIO), C.c_double, C.c_double, vp]
-        L.jm_compose_plan_create.argtypes = [C.POINTER(_abi.ComposeDesc), C.POINTER(vp)]
-        L.jm_compose_plan_destroy.argtypes = [vp]
         L.jm_block_compose.argtypes = [vp, C.c_int32, C.c_int64, C.POINTER(_abi.ComposeIO), C.c_int32, vp]
-        L.jm_observe_plan_create.argtypes = [C.POINTER(_abi.ObserveDesc), C.POINTER(vp)]
-        L.jm_observe_plan_destroy.argtypes = [vp]
         L.jm_block_observe.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, C.POINTER(_abi.ObserveIO), C.c_int32, vp]
+        for family, desc in _abi.PLAN_FAMILIES.items():
+            getattr(L, f"jm_{family}_plan_create").argtypes = [C.POINTER(desc), C.POINTER(vp)]
+            getattr(L, f"jm_{family}_plan_destroy").argtypes = [vp]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ("jm_topology_signature",):

@@ -77,7 +77,78 @@ import torch
 EARTH_SURFACE_GRAVITY = 9.81
 
 
-class HipBlocks:
+class _EngineBlock:
+    """What every block bound to an engine repeats: the binding, the tensor check and the mask normalisation.  The
+    constructor does nothing: a subclass validates its arguments first and calls `_bind` where it starts to build."""
+
+    def _bind(self, engine) -> None:
+        """The engine's topology library, error check and dtype code."""
+        import ctypes as C
+
+        from . import _abi
+        self._C = C
+        self._eng = engine
+        self._L = engine._lib.L
+        self._check = engine._lib.check
+        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+
+    def _ptr(self, t: Optional[torch.Tensor], dtype=None) -> Optional[int]:
+        """The data pointer of a contiguous tensor on the engine's device, of the engine's dtype unless `dtype` names
+        another.  None for None and for a tensor without elements (`FootPoseQuantities` with one foot has no relative
+        column): the library receives a null pointer, its sign for an absent input or output."""
+        if t is None:
+            return None
+        eng = self._eng
+        if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
+            raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
+        return t.data_ptr() if t.numel() else None
+
+    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """A lane mask of any dtype as the contiguous uint8 `[B]` tensor on the engine's device the kernels read."""
+        if lane_mask is None:
+            return None
+        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
+        if tuple(mask.shape) != (self._eng.batch_size,):
+            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
+        return mask
+
+    def _flags(self, t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+        """Per-lane flags a launch reads as they are: bool or uint8 `[B]`, no conversion (a bool tensor is viewed as bytes)."""
+        if t is None:
+            return None
+        if t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        B = self._eng.batch_size
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != self._eng.device or tuple(t.shape) != (B,):
+            raise ValueError(f"{name} must be a contiguous bool or uint8 tensor of shape ({B},) on the engine's device")
+        return t
+
+
+class _PlanBlock(_EngineBlock):
+    """A block driven by a plan of the library: `self.plan` (a host plan with `desc()`) is created on the device once by
+    `jm_<family>_plan_create` and destroyed with the object by `jm_<family>_plan_destroy` (`_abi.PLAN_FAMILIES`)."""
+
+    def _create_plan(self, family: str) -> None:
+        from . import _abi
+        C = self._C
+        assert family in _abi.PLAN_FAMILIES, family     # (the loader declares the entry points of these families only)
+        desc, keep = self.plan.desc()
+        self._family, self._plan = family, C.c_void_p()
+        with torch.cuda.device(self._eng.device):
+            self._check(getattr(self._L, f"jm_{family}_plan_create")(C.byref(desc), C.byref(self._plan)))
+        del keep        # (the library copied the description)
+
+    def __del__(self) -> None:
+        # (safe on a half-built object -- no `_plan`, or a null one after a failed create -- and never twice)
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            try:
+                getattr(self._L, f"jm_{self._family}_plan_destroy")(plan)
+            except Exception:       # noqa: BLE001  (interpreter shutdown)
+                pass
+
+
+class HipBlocks(_EngineBlock):
     """Per-controller-tick pipeline blocks as single HIP kernel launches (`jm_block_*`).
 
     Bound to one engine: uses its topology library, device, dtype and launch stream.  All tensors
@@ -85,15 +156,8 @@ class HipBlocks:
 
     def __init__(self, engine, encoder_index, command_state_lower, command_state_upper, kp, kd,
                  motors_effort_limit) -> None:
-        import ctypes as C
-
         import numpy as np
-        from . import _abi
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
 
         def host(x, shape):
             a = np.ascontiguousarray(torch.as_tensor(x).detach().cpu().numpy(), dtype=np.float64)
@@ -105,11 +169,6 @@ class HipBlocks:
         self._enc = np.ascontiguousarray(torch.as_tensor(encoder_index).cpu().numpy(), dtype=np.int32)
         self._lo, self._hi = host(command_state_lower, (3, M)), host(command_state_upper, (3, M))
         self._kp, self._kd, self._lim = host(kp, (M,)), host(kd, (M,)), host(motors_effort_limit, (M,))
-
-    def _ptr(self, t: torch.Tensor):
-        if not t.is_contiguous() or t.device != self._eng.device or t.dtype != self._eng.dtype:
-            raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-        return self._C.c_void_p(t.data_ptr())
 
     def pd_controller(self, command_state: torch.Tensor, control_dt: float, out: torch.Tensor) -> None:
         """≙ `pd_controller` (proportional_derivative_controller.py:101-163) on the engine's raw
@@ -162,7 +221,7 @@ class HipBlocks:
             self._eng._stream()))
 
 
-class DeformationEstimator:
+class DeformationEstimator(_PlanBlock):
     """≙ `gym_jiminy.common.blocks.DeformationEstimator` (blocks/deformation_estimator.py:416-863), batched: from the
     encoders of the engine and IMU attitude estimates (`[4][n_imu][B]` xyzw in the order of the model's IMU sensors, e.g.
     the state of the Mahony filter) to one deformation quaternion per flexibility point.
@@ -173,14 +232,8 @@ class DeformationEstimator:
     joint at every frame of `flex_frame_names` (`NotImplementedError` otherwise; see jiminy_amd/deformation.py)."""
 
     def __init__(self, engine, imu_frame_names, flex_frame_names, ignore_twist: bool = True, compute_rpy: bool = True) -> None:
-        import ctypes as C
-
-        from . import _abi, deformation
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        from . import deformation
+        self._bind(engine)
         self.plan = deformation.build_plan(engine.model, imu_frame_names, flex_frame_names, ignore_twist, compute_rpy)
         self.ignore_twist, self.compute_rpy = bool(ignore_twist), bool(compute_rpy)
         self.flexibility_frame_names = list(self.plan.flexibility_frame_names)
@@ -189,11 +242,7 @@ class DeformationEstimator:
         self.quat = torch.zeros((4, n_flex, B), dtype=engine.dtype, device=engine.device)
         self.quat[3] = 1.0
         self.rpy = torch.zeros((3, n_flex, B), dtype=engine.dtype, device=engine.device) if compute_rpy else None
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_deform_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("deform")
 
     @property
     def fieldnames(self):
@@ -222,29 +271,12 @@ class DeformationEstimator:
         eng = self._eng
         if tuple(imu_quat.shape) != (4, self._n_imu, eng.batch_size):
             raise ValueError(f"imu_quat must have shape (4, {self._n_imu}, {eng.batch_size})")
-        for t in (imu_quat, self.quat):
-            if not t.is_contiguous() or t.device != eng.device or t.dtype != eng.dtype:
-                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-        vp = self._C.c_void_p
         self._check(self._L.jm_block_deformation_estimator(
-            self._plan, self._dtype, eng.batch_size, vp(eng.field("encoder").data_ptr()), vp(imu_quat.data_ptr()),
-            vp(self.quat.data_ptr()), None if self.rpy is None else vp(self.rpy.data_ptr()), eng._stream()))
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_deform_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
+            self._plan, self._dtype, eng.batch_size, self._ptr(eng.field("encoder")), self._ptr(imu_quat),
+            self._ptr(self.quat), self._ptr(self.rpy), eng._stream()))
 
 
-def _check_block_tensor(eng, t: torch.Tensor) -> None:
-    if not t.is_contiguous() or t.device != eng.device or t.dtype != eng.dtype:
-        raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-
-
-class MahonyFilter:
+class MahonyFilter(_PlanBlock):
     """≙ `gym_jiminy.common.blocks.MahonyFilter` (blocks/mahony_filter.py:104-393), batched over the IMU sensors of the
     engine's model (sensor order) and its lanes.
 
@@ -255,14 +287,8 @@ class MahonyFilter:
 
     def __init__(self, engine, *, ignore_twist: bool = False, exact_init: bool = True, kp=1.0, ki=0.1,
                  compute_rpy: bool = False) -> None:
-        import ctypes as C
-
-        from . import _abi, attitude
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        from . import attitude
+        self._bind(engine)
         self.plan = attitude.build_plan(engine.model, kp, ki)
         self.ignore_twist, self.exact_init, self.compute_rpy = bool(ignore_twist), bool(exact_init), bool(compute_rpy)
         self.kp, self.ki = self.plan.kp, self.plan.ki
@@ -272,11 +298,7 @@ class MahonyFilter:
         self.quat[3] = 1.0      # (:286)
         self.rpy = new(3) if compute_rpy else None
         self._twist_of = None   # the `twist` state of a BodyObserver behind this filter: zeroed by the same launch
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_attitude_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("attitude")
 
     @property
     def fieldnames(self):
@@ -288,40 +310,22 @@ class MahonyFilter:
             names["rpy"] = [[f"{n}.{e}" for n in imu] for e in ("Roll", "Pitch", "Yaw")]
         return names
 
-    def _vp(self, t: Optional[torch.Tensor]):
-        if t is None:
-            return None
-        _check_block_tensor(self._eng, t)
-        return self._C.c_void_p(t.data_ptr())
-
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
-        eng = self._eng
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
+        eng, ptr = self._eng, self._ptr
+        mask = self._mask(lane_mask)
         twist = None if self._twist_of is None else self._twist_of.twist
         self._check(self._L.jm_block_attitude_init(
-            self._plan, self._dtype, eng.batch_size, self._vp(eng.field("q")), self._vp(eng.field("imu")),
-            None if mask is None else self._C.c_void_p(mask.data_ptr()), int(self.exact_init), self._vp(self.quat),
-            self._vp(self.omega), self._vp(self._cf), self._vp(self.bias), self._vp(twist), self._vp(self.rpy), eng._stream()))
+            self._plan, self._dtype, eng.batch_size, ptr(eng.field("q")), ptr(eng.field("imu")), ptr(mask, torch.uint8),
+            int(self.exact_init), ptr(self.quat), ptr(self.omega), ptr(self._cf), ptr(self.bias), ptr(twist), ptr(self.rpy),
+            eng._stream()))
 
     def refresh(self, dt: float) -> None:
-        eng = self._eng
+        eng, ptr = self._eng, self._ptr
         if not dt > 0.0:
             raise ValueError("This block does not support time-continuous update.")     # (:288-291)
         self._check(self._L.jm_block_mahony_observer(
-            self._plan, self._dtype, eng.batch_size, self._vp(eng.field("imu")), self._vp(self.quat), self._vp(self.omega),
-            self._vp(self._cf), self._vp(self.bias), float(dt), int(self.ignore_twist), self._vp(self.rpy), eng._stream()))
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_attitude_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
+            self._plan, self._dtype, eng.batch_size, ptr(eng.field("imu")), ptr(self.quat), ptr(self.omega),
+            ptr(self._cf), ptr(self.bias), float(dt), int(self.ignore_twist), ptr(self.rpy), eng._stream()))
 
 
 class BodyObserver:
@@ -393,8 +397,8 @@ class BodyObserver:
         mode = self._mode if integrate or self._mode != attitude.TWIST_INTEGRATE else attitude.TWIST_REMOVE
         tci = self.twist_time_constant_inv if mode == attitude.TWIST_INTEGRATE else 0.0
         m._check(m._L.jm_block_body_observer(
-            m._plan, m._dtype, eng.batch_size, m._vp(m.quat), m._vp(m.omega), m._vp(quat), m._vp(omega),
-            m._vp(self.twist), int(mode), float(tci), float(dt), m._vp(rpy), eng._stream()))
+            m._plan, m._dtype, eng.batch_size, m._ptr(m.quat), m._ptr(m.omega), m._ptr(quat), m._ptr(omega),
+            m._ptr(self.twist), int(mode), float(tci), float(dt), m._ptr(rpy), eng._stream()))
 
 
 def frame_fieldnames(frame_names, compute_rpy: bool, compute_velocity: bool, average: bool):
@@ -414,7 +418,7 @@ def frame_fieldnames(frame_names, compute_rpy: bool, compute_velocity: bool, ave
     return names
 
 
-class FrameKinematics:
+class FrameKinematics(_PlanBlock):
     """Pose and velocity of named frames of the engine's model, per lane, and their average over an environment step.
 
     ≙ `FramePosition` / `FrameOrientation` / `FrameXYZQuat` (quantities/generic.py:298-950) for `pose` `[7][K][B]` (x y z,
@@ -437,11 +441,7 @@ class FrameKinematics:
 
     def __init__(self, engine, frame_names, *, reference_frames=None, compute_rpy: bool = False, compute_velocity: bool = True,
                  average: bool = False, state=None) -> None:
-        import ctypes as C
-
-        from . import _abi, frames
-        self._C = C
-        self._eng = engine
+        from . import frames
         # `state`: a pair (q, v) of `[rows][B]` tensors read instead of the engine's fields (v may be None without
         # `compute_velocity`) -- the state of a reference trajectory, which the reference evaluates on the trajectory's own
         # robot, not on the per-episode biased model: the lane's joint placements are not applied then
@@ -455,9 +455,7 @@ class FrameKinematics:
             if v is None and compute_velocity:
                 raise ValueError("the frame velocity needs v: give state=(q, v) or compute_velocity=False")
             self._state = (q, v)
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
         self.plan = frames.build_plan(engine.model, frame_names, reference_frames)
         self.frame_names = list(self.plan.frame_names)
         self.compute_rpy, self.compute_velocity, self.average = bool(compute_rpy), bool(compute_velocity), bool(average)
@@ -474,11 +472,7 @@ class FrameKinematics:
             self.average_velocity, self.pose_mean, self.quat_no_yaw, self.pose_prev = new(6), new(7), new(4), new(7)
             for t in (self.pose_mean[6], self.quat_no_yaw[3], self.pose_prev[6]):
                 t.fill_(1.0)
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_frames_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("frames")
 
     def index(self, frame_name: str) -> int:
         """Column of a frame in the tensors."""
@@ -488,35 +482,21 @@ class FrameKinematics:
     def fieldnames(self):
         return frame_fieldnames(self.frame_names, self.compute_rpy, self.compute_velocity, self.average)
 
-    def _vp(self, t: Optional[torch.Tensor]):
-        if t is None:
-            return None
-        _check_block_tensor(self._eng, t)
-        return self._C.c_void_p(t.data_ptr())
-
     def _kinematics(self, mask: Optional[torch.Tensor], pose_prev: Optional[torch.Tensor]) -> None:
-        eng = self._eng
+        eng, ptr = self._eng, self._ptr
         if self._state is not None:
             q, v, model_lane = self._state[0], self._state[1], None
         else:
             q, v, model_lane = eng.field("q"), eng.field("v"), eng._fields.get("model_lane")
         self._check(self._L.jm_block_frame_kinematics(
-            self._plan, self._dtype, eng.batch_size, self._vp(q),
-            self._vp(v) if self.compute_velocity else None, self._vp(model_lane),
-            None if mask is None else self._C.c_void_p(mask.data_ptr()), self._vp(self.pose), self._vp(pose_prev),
-            self._vp(self.rpy), self._vp(self.velocity), eng._stream()))
+            self._plan, self._dtype, eng.batch_size, ptr(q), ptr(v) if self.compute_velocity else None, ptr(model_lane),
+            ptr(mask, torch.uint8), ptr(self.pose), ptr(pose_prev), ptr(self.rpy), ptr(self.velocity), eng._stream()))
 
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         """The frames at the state of a new episode on the masked lanes (every lane without a mask), which also becomes
         the previous pose of their step average.  The other lanes keep every tensor bit for bit.  Call it after the
         engine's `start` / `reset_lanes`."""
-        eng = self._eng
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
-        self._kinematics(mask, self.pose_prev)
+        self._kinematics(self._mask(lane_mask), self.pose_prev)
 
     def refresh(self) -> None:
         """One launch on the engine's stream: `pose`, `rpy`, `velocity` at the engine's `q`, `v`."""
@@ -529,21 +509,13 @@ class FrameKinematics:
             raise RuntimeError("this block was built without average=True")
         if not step_dt > 0.0:
             raise ValueError("the step average needs a positive step_dt")
-        eng = self._eng
+        eng, ptr = self._eng, self._ptr
         self._check(self._L.jm_block_frame_average(
-            self._plan, self._dtype, eng.batch_size, self._vp(self.pose_prev), self._vp(self.pose), 1.0 / float(step_dt),
-            self._vp(self.average_velocity), self._vp(self.pose_mean), self._vp(self.quat_no_yaw), eng._stream()))
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_frames_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
+            self._plan, self._dtype, eng.batch_size, ptr(self.pose_prev), ptr(self.pose), 1.0 / float(step_dt),
+            ptr(self.average_velocity), ptr(self.pose_mean), ptr(self.quat_no_yaw), eng._stream()))
 
 
-class CentroidalState:
+class CentroidalState(_PlanBlock):
     """The centroidal quantities of a state other than the engine's own: `centroidal` `[15][B]` in the row layout of the
     engine's `centroidal` field -- com (3), hg (6: linear then angular, about the centre of mass, world axes), dhg (6) -- from
     `state=(q, v, a)`, `[rows][B]` tensors in pinocchio's convention (`ReferenceTrajectory.q` / `.v` / `.a`); `a` may be None:
@@ -557,10 +529,9 @@ class CentroidalState:
     identity."""
 
     def __init__(self, engine, state) -> None:
-        import ctypes as C
         import os
 
-        from . import _abi, centroidal
+        from . import centroidal
         if os.environ.get("JIMINY_AMD_TENSOR_BLOCKS", "0") == "1":
             raise NotImplementedError("the centroidal state has no tensor-program form (JIMINY_AMD_TENSOR_BLOCKS=1): "
                                       "the evaluation exists as the HIP kernel only")
@@ -571,20 +542,13 @@ class CentroidalState:
                 continue
             if t is None or tuple(t.shape) != (rows, B):
                 raise ValueError(f"state {name} must have shape ({rows}, {B})")
-        self._C = C
-        self._eng, self._state = engine, (q, v, a)
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
+        self._state = (q, v, a)
         self.plan = centroidal.build_plan(model)
         self.mass = self.plan.mass
         self.has_acceleration = a is not None
         self.centroidal = torch.zeros((centroidal.ROWS, B), dtype=engine.dtype, device=engine.device)
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_centroidal_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("centroidal")
 
     @property
     def fieldnames(self):
@@ -592,41 +556,21 @@ class CentroidalState:
         return {"centroidal": [f"Com.{e}" for e in xyz] + [f"{h}.{k}{e}" for h in ("Momentum", "MomentumRate") for k in ("Lin", "Ang")
                                                              for e in xyz]}
 
-    def _vp(self, t: Optional[torch.Tensor]):
-        if t is None:
-            return None
-        _check_block_tensor(self._eng, t)
-        return self._C.c_void_p(t.data_ptr())
-
     def _launch(self, mask: Optional[torch.Tensor]) -> None:
-        eng = self._eng
+        eng, ptr = self._eng, self._ptr
         q, v, a = self._state
         self._check(self._L.jm_block_centroidal_state(
-            self._plan, self._dtype, eng.batch_size, self._vp(q), self._vp(v), self._vp(a),
-            None if mask is None else self._C.c_void_p(mask.data_ptr()), self._vp(self.centroidal), eng._stream()))
+            self._plan, self._dtype, eng.batch_size, ptr(q), ptr(v), ptr(a), ptr(mask, torch.uint8), ptr(self.centroidal),
+            eng._stream()))
 
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         """The quantities at the state tensors on the masked lanes (every lane without a mask); the other lanes keep every
         bit."""
-        eng = self._eng
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
-        self._launch(mask)
+        self._launch(self._mask(lane_mask))
 
     def refresh(self) -> None:
         """One launch on the engine's stream: `centroidal` at the state tensors."""
         self._launch(None)
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_centroidal_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
 
 LOCOMOTION_SCALARS = ("force_vertical_max", "ground_distance_min", "reward_momentum", "reward_friction")
@@ -648,7 +592,7 @@ def locomotion_fieldnames(contact_names, foot_frame_names, momentum: bool, force
     return names
 
 
-class LocomotionQuantities:
+class LocomotionQuantities(_PlanBlock):
     """The balance quantities of the reference's locomotion layer (quantities/locomotion.py, compositions/locomotion.py) per
     lane, from what a step left on the device: `com`, `vcom` `[3][B]` ≙ `CenterOfMass` (:814-887); `odom_pose` `[3][B]` ≙
     `BaseOdometryPose` (:158-219); `zmp` `[2][B]` ≙ `ZeroMomentPoint` (:914-1017; NaN in free fall); `dcm` `[2][B]` ≙
@@ -688,8 +632,6 @@ class LocomotionQuantities:
     def __init__(self, engine, frames: "FrameKinematics", *, foot_frame_names="auto", zmp_reference_frame="LOCAL",
                  dcm_reference_frame="LOCAL", momentum_cutoff: Optional[float] = None, friction_cutoff: Optional[float] = None,
                  momentum: bool = True, forces: bool = True, state=None, ground_profile: bool = False) -> None:
-        import ctypes as C
-
         from . import _abi, locomotion
         from . import frames as frames_
         model = engine.model
@@ -741,11 +683,8 @@ class LocomotionQuantities:
         if self.momentum and frames.plan.modes[frames.index("root_joint")] != frames_.LOCAL:
             raise ValueError("the angular momentum reads the LOCAL step-average velocity of 'root_joint': the frame kinematics "
                              "block holds it in another reference frame")
-        self._C = C
-        self._eng, self._frames = engine, frames
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
+        self._frames = frames
         self.foot_frame_names = list(self.plan.foot_frame_names)
         self.momentum_cutoff = None if momentum_cutoff is None else float(momentum_cutoff)
         self.friction_cutoff = None if friction_cutoff is None else float(friction_cutoff)
@@ -763,11 +702,7 @@ class LocomotionQuantities:
         self._flag_row, self._lambda_row = rows["n_bounds"], 2 * rows["n_bounds"]
         self._q_row = int(model.idx_q[1])
         self._io = _abi.LocomotionIO()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_locomotion_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("locomotion")
 
     @property
     def fieldnames(self):
@@ -790,14 +725,7 @@ class LocomotionQuantities:
         return self.scalars[3]
 
     def _launch(self, mask: Optional[torch.Tensor]) -> None:
-        eng, fr, io = self._eng, self._frames, self._io
-
-        def ptr(t: Optional[torch.Tensor], dtype=None):
-            if t is None:
-                return None
-            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
-                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-            return t.data_ptr()
+        eng, fr, io, ptr = self._eng, self._frames, self._io, self._ptr
         if self._state is not None:
             q, centroidal = self._state
             io.centroidal, io.q_root, io.model_lane = ptr(centroidal), ptr(q[self._q_row:self._q_row + 7]), None
@@ -814,7 +742,7 @@ class LocomotionQuantities:
         io.v_avg = ptr(fr.average_velocity) if self.momentum else None
         io.quat_no_yaw = ptr(fr.quat_no_yaw) if self.momentum else None
         io.pose = ptr(fr.pose)
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = ptr(mask, torch.uint8)
         for name in ("com", "vcom", "odom_pose", "zmp", "dcm", "h_angular", "contact_force_rel", "foot_force_vertical", "scalars"):
             setattr(io, name, ptr(getattr(self, name)))
         if not self.ground_profile:
@@ -834,25 +762,11 @@ class LocomotionQuantities:
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         """The quantities at the state of a new episode on the masked lanes (every lane without a mask); the other lanes
         keep every tensor bit for bit.  Call it after the engine's `start` / `reset_lanes` and the reset of `frames`."""
-        eng = self._eng
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
-        self._launch(mask)
+        self._launch(self._mask(lane_mask))
 
     def refresh(self) -> None:
         """One launch on the engine's stream, behind the refresh (and the step average) of `frames`."""
         self._launch(None)
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_locomotion_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
 
 ACTUATION_SCALARS = ("power", "power_average", "reward_power")
@@ -867,7 +781,7 @@ def actuation_fieldnames(motor_names):
     return names
 
 
-class ActuatedJointQuantities:
+class ActuatedJointQuantities(_PlanBlock):
     """The actuated-joint part of the reference's quantity layer (quantities/generic.py:1538-1887, compositions/generic.py:
     153-191, 456-661) per lane, from the engine's `q / v / a / command`, each tensor in motor order: `position`, `velocity`,
     `acceleration` `[M][B]` ≙ `MultiActuatedJointKinematic` (:1538-1691; `motor_side`: all three times the mechanical reduction);
@@ -889,8 +803,6 @@ class ActuatedJointQuantities:
     def __init__(self, engine, *, generator_mode="CHARGE", power_horizon: Optional[float] = None,
                  power_cutoff: Optional[float] = None, position_margin: Optional[float] = None,
                  velocity_max: Optional[float] = None, motor_side: bool = False, step_dt: Optional[float] = None) -> None:
-        import ctypes as C
-
         from . import _abi, actuation
         if power_cutoff is not None and not float(power_cutoff) > 0.0:
             raise ValueError("a reward cutoff must be positive")
@@ -901,11 +813,7 @@ class ActuatedJointQuantities:
         if velocity_max is not None and (not float(velocity_max) >= 0.0 or not float(position_margin) >= 0.0):
             raise ValueError("position_margin and velocity_max must not be negative")
         self.plan = actuation.build_plan(engine.model, generator_mode=generator_mode, power_horizon=power_horizon, step_dt=step_dt)
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
         self.motor_side = bool(motor_side)
         self.power_cutoff = None if power_cutoff is None else float(power_cutoff)
         self.position_margin = None if position_margin is None else float(position_margin)
@@ -916,11 +824,7 @@ class ActuatedJointQuantities:
         self.scalars, self.safety = new(3), new(dtype=torch.int32)
         self.power_ring, self.power_count = new(self.plan.max_stack), new(dtype=torch.int32)
         self._io = _abi.ActuationIO()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_actuation_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("actuation")
 
     @property
     def fieldnames(self):
@@ -943,15 +847,10 @@ class ActuatedJointQuantities:
         return self.scalars[2]
 
     def _launch(self, mode: int, mask: Optional[torch.Tensor]) -> None:
-        eng, io = self._eng, self._io
-
-        def ptr(t: torch.Tensor, dtype=None):
-            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
-                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-            return t.data_ptr()
+        eng, io, ptr = self._eng, self._io, self._ptr
         for name in ("q", "v", "a", "command"):
             setattr(io, name, ptr(eng.field(name)))
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = ptr(mask, torch.uint8)
         for name in ("position", "velocity", "acceleration", "bound_low", "bound_high", "scalars"):
             setattr(io, name, ptr(getattr(self, name)))
         io.safety = ptr(self.safety, torch.int32) if self.velocity_max is not None else None
@@ -968,26 +867,12 @@ class ActuatedJointQuantities:
         episode; the other lanes keep every tensor, the ring and the counter bit for bit.  Call it after the engine's `start`
         / `reset_lanes`."""
         from . import actuation
-        eng = self._eng
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
-        self._launch(actuation.RESTART, mask)
+        self._launch(actuation.RESTART, self._mask(lane_mask))
 
     def refresh(self) -> None:
         """One launch on the engine's stream: the quantities at the engine's state, pushed into the window of every lane."""
         from . import actuation
         self._launch(actuation.PUSH, None)
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_actuation_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
 
 FOOTPOSES_SCALARS = ("reward_foot_positions", "reward_foot_orientations")
@@ -1004,7 +889,7 @@ def footposes_fieldnames(foot_frame_names):
             "scalars": list(FOOTPOSES_SCALARS)}
 
 
-class FootPoseQuantities:
+class FootPoseQuantities(_PlanBlock):
     """The foot pose quantities of the reference's locomotion layer per lane, from the `pose` of a `FrameKinematics`, F feet in
     the order of `foot_frame_names` (sorted, `sanitize_foot_frame_names`): `mean_pose` `[7][B]` ≙ `MultiFootMeanXYZQuat`
     (quantities/locomotion.py:416-478; quantities/generic.py:950-1062); `mean_odom_pose` `[3][B]` ≙ `MultiFootMeanOdometryPose`
@@ -1028,8 +913,6 @@ class FootPoseQuantities:
 
     def __init__(self, engine, frames: "FrameKinematics", *, foot_frame_names="auto", position_cutoff: Optional[float] = None,
                  orientation_cutoff: Optional[float] = None) -> None:
-        import ctypes as C
-
         from . import _abi, footposes
         if not engine.model.has_freeflyer:
             raise ValueError("Only legged robot with floating base are supported: the model has no free-flyer.")
@@ -1039,11 +922,8 @@ class FootPoseQuantities:
             if cutoff is not None and not float(cutoff) > 0.0:
                 raise ValueError("a reward cutoff must be positive")
         self.plan = footposes.build_plan(engine.model, frames.frame_names, foot_frame_names)
-        self._C = C
-        self._eng, self._frames = engine, frames
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
+        self._frames = frames
         self.foot_frame_names = list(self.plan.foot_frame_names)
         self.position_cutoff = None if position_cutoff is None else float(position_cutoff)
         self.orientation_cutoff = None if orientation_cutoff is None else float(orientation_cutoff)
@@ -1054,11 +934,7 @@ class FootPoseQuantities:
         for t in (self.mean_pose, self.relative_pose, self.reference_relative_pose):
             t[6] = 1.0
         self._io = _abi.FootPosesIO()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_footposes_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("footposes")
 
     @property
     def fieldnames(self):
@@ -1076,23 +952,11 @@ class FootPoseQuantities:
             raise ValueError("the block has no orientation reward: build it with orientation_cutoff")
         return self.scalars[1]
 
-    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        if lane_mask is None:
-            return None
-        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
-        if tuple(mask.shape) != (self._eng.batch_size,):
-            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
-        return mask
-
     def _launch(self, mask: Optional[torch.Tensor]) -> None:
-        eng, io = self._eng, self._io
-
-        def ptr(t: torch.Tensor):
-            if not t.is_contiguous() or t.device != eng.device or t.dtype != eng.dtype:
-                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-            return t.data_ptr() if t.numel() else None        # (one foot: the relative tensors have no column)
+        eng, io, ptr = self._eng, self._io, self._ptr
         io.pose = ptr(self._frames.pose)
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = ptr(mask, torch.uint8)
+        # (one foot: the relative tensors have no column and go in as null pointers)
         for name in ("reference_relative_pose", "mean_pose", "mean_odom_pose", "relative_pose", "tracking_error", "scalars"):
             setattr(io, name, ptr(getattr(self, name)))
         self._check(self._L.jm_block_foot_poses(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
@@ -1116,14 +980,6 @@ class FootPoseQuantities:
         """One launch on the engine's stream, behind the refresh of `frames`."""
         self._launch(None)
 
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_footposes_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
-
 
 def support_fieldnames(contact_names):
     """Names of the rows of the tensors of a `SupportPolygon` block (`vertex_index` counts in `contact_names`)."""
@@ -1134,7 +990,7 @@ def support_fieldnames(contact_names):
             "points": list(contact_names)}
 
 
-class SupportPolygon:
+class SupportPolygon(_PlanBlock):
     """The projected support polygon of the reference's toolbox per lane (toolbox/quantities/locomotion.py:22-239,
     toolbox/math/qhull.py, toolbox/compositions/locomotion.py:15-115), from the `pose` of a `FrameKinematics` and the `zmp` /
     `odom_pose` of a `LocomotionQuantities`: `n_vertices` `[B]` and `vertex_index` `[16][B]` (int32; indices into the model's
@@ -1163,8 +1019,6 @@ class SupportPolygon:
 
     def __init__(self, engine, frames: "FrameKinematics", locomotion: "LocomotionQuantities", *, reference_frame=None,
                  cutoff_inner: Optional[float] = None, cutoff_outer: Optional[float] = None) -> None:
-        import ctypes as C
-
         from . import _abi, support
         from .locomotion import odometry_frame
         support.check_model(engine.model)
@@ -1188,11 +1042,8 @@ class SupportPolygon:
             names = ("LOCAL", "LOCAL_WORLD_ALIGNED")
             raise ValueError(f"reference_frame {names[frame]} differs from the zmp_reference_frame {names[zmp_frame]} of the "
                              "locomotion quantities block: the margin is evaluated in one frame")
-        self._C = C
-        self._eng, self._frames, self._locomotion = engine, frames, locomotion
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
+        self._frames, self._locomotion = frames, locomotion
         self.reference_frame = frame
         self.contact_names = list(self.plan.contact_names)
         self.cutoff_inner = None if cutoff_inner is None else float(cutoff_inner)
@@ -1203,11 +1054,7 @@ class SupportPolygon:
         self.vertices, self.center = new(2, M), new(2)
         self.scalars = new(2) if locomotion.zmp is not None else None
         self._io = _abi.SupportIO()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_support_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("support")
 
     @property
     def fieldnames(self):
@@ -1226,16 +1073,9 @@ class SupportPolygon:
         return self.scalars[1]
 
     def _launch(self, mask: Optional[torch.Tensor]) -> None:
-        eng, io, loco = self._eng, self._io, self._locomotion
-
-        def ptr(t: Optional[torch.Tensor], dtype=None):
-            if t is None:
-                return None
-            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
-                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-            return t.data_ptr()
+        eng, io, loco, ptr = self._eng, self._io, self._locomotion, self._ptr
         io.pose, io.odom_pose, io.zmp = ptr(self._frames.pose), ptr(loco.odom_pose), ptr(loco.zmp)
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = ptr(mask, torch.uint8)
         io.n_vertices, io.vertex_index = ptr(self.n_vertices, torch.int32), ptr(self.vertex_index, torch.int32)
         io.vertices, io.center, io.scalars = ptr(self.vertices), ptr(self.center), ptr(self.scalars)
         self._check(self._L.jm_block_support_polygon(self._plan, self._dtype, eng.batch_size, self._C.byref(io),
@@ -1244,24 +1084,11 @@ class SupportPolygon:
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         """The quantities at the state of a new episode on the masked lanes (every lane without a mask); the other lanes
         keep every tensor bit for bit.  Call it after the reset of `frames` and of `locomotion`."""
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (self._eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
-        self._launch(mask)
+        self._launch(self._mask(lane_mask))
 
     def refresh(self) -> None:
         """One launch on the engine's stream, behind the refresh of `frames` and of `locomotion`."""
         self._launch(None)
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_support_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
 
 def tracking_fieldnames(foot_frame_names, motor_names):
@@ -1274,7 +1101,7 @@ def tracking_fieldnames(foot_frame_names, motor_names):
             "reference_position": [f"{n}.ReferencePosition" for n in motor_names], "scalars": list(SCALARS)}
 
 
-class TrackingWindows:
+class TrackingWindows(_PlanBlock):
     """The trajectory-tracking windows of the reference's composition layer per lane, over sliding windows of environment
     steps: `delta_odom`, `delta_odom_reference` `[3][B]` ≙ `DeltaBaseOdometryPosition` / `DeltaBaseOdometryOrientation`
     (quantities/locomotion.py:1537-1693) of the true and of the reference odometry pose; `scalars` `[6][B]`, rows
@@ -1304,8 +1131,6 @@ class TrackingWindows:
                  actuation: Optional["ActuatedJointQuantities"] = None, odometry_horizon: Optional[float] = None,
                  foot_horizon: Optional[float] = None, motor_horizon: Optional[float] = None,
                  odometry_cutoff: Optional[float] = None, step_dt: float) -> None:
-        import ctypes as C
-
         from . import _abi, tracking
         for horizon, block, what, keyword in ((odometry_horizon, locomotion, "odometry_horizon", "locomotion"),
                                               (foot_horizon, foot_poses, "foot_horizon", "foot_poses"),
@@ -1324,11 +1149,7 @@ class TrackingWindows:
                                         motor_horizon=motor_horizon,
                                         n_feet=None if foot_horizon is None else foot_poses.plan.n_feet,
                                         n_motors=None if motor_horizon is None else actuation.plan.n_motors)
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
         self._locomotion = locomotion if odometry_horizon is not None else None
         self._foot_poses = foot_poses if foot_horizon is not None else None
         self._actuation = actuation if motor_horizon is not None else None
@@ -1349,11 +1170,7 @@ class TrackingWindows:
         if p.max_stack_motor:
             self.reference_position, self.motor_ring = new(p.n_motors), new(p.max_stack_motor)
         self._io = _abi.TrackingIO()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_tracking_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep
+        self._create_plan("tracking")
 
     @property
     def fieldnames(self):
@@ -1397,28 +1214,13 @@ class TrackingWindows:
     def shift_motor_positions(self) -> torch.Tensor:
         return self._scalar(5, self._actuation is not None, "motor_horizon")
 
-    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        if lane_mask is None:
-            return None
-        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
-        if tuple(mask.shape) != (self._eng.batch_size,):
-            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
-        return mask
-
     def _launch(self, mode: int, mask: Optional[torch.Tensor]) -> None:
-        eng, io = self._eng, self._io
-
-        def ptr(t: Optional[torch.Tensor], dtype=None):
-            if t is None:
-                return None
-            if not t.is_contiguous() or t.device != eng.device or t.dtype != (dtype or eng.dtype):
-                raise ValueError("pipeline block tensors must be contiguous engine-dtype tensors on the engine's device")
-            return t.data_ptr()
+        eng, io, ptr = self._eng, self._io, self._ptr
         io.odom_pose = ptr(self._locomotion.odom_pose) if self._locomotion is not None else None
         io.relative_pose = ptr(self._foot_poses.relative_pose) if self._foot_poses is not None else None
         io.reference_relative_pose = ptr(self._foot_poses.reference_relative_pose) if self._foot_poses is not None else None
         io.position = ptr(self._actuation.position) if self._actuation is not None else None
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = ptr(mask, torch.uint8)
         io.count = ptr(self.count, torch.int32)
         for name in ("reference_odom_pose", "reference_position", "odom_ring", "yaw_prev", "yaw_ring", "foot_ring", "motor_ring",
                      "delta_odom", "delta_odom_reference", "scalars"):
@@ -1456,14 +1258,6 @@ class TrackingWindows:
         from . import tracking
         self._launch(tracking.PUSH, None)
 
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_tracking_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
-
 
 def trajectory_fieldnames(model, fields: int, motor_names):
     """Names of the rows of the tensors of a `ReferenceTrajectory` block."""
@@ -1479,7 +1273,7 @@ def trajectory_fieldnames(model, fields: int, motor_names):
     return names
 
 
-class ReferenceTrajectory:
+class ReferenceTrajectory(_PlanBlock):
     """The state of a recorded trajectory at every lane's own time: what `QuantityEvalMode.REFERENCE` reads.  ≙
     `DatasetTrajectoryQuantity` (bases/quantities.py:870-1210) over `Trajectory.get` (jiminy_py/dynamics.py:296-388).
 
@@ -1503,7 +1297,6 @@ class ReferenceTrajectory:
     `ActuatedJointQuantities` block) names the motors of `position`; default: the model's."""
 
     def __init__(self, engine, dataset, *, actuation: Optional["ActuatedJointQuantities"] = None) -> None:
-        import ctypes as C
         import os
 
         import numpy as np
@@ -1519,11 +1312,7 @@ class ReferenceTrajectory:
         self.names = list(self.plan.names)
         self._motor_names = list(actuation.plan.motor_names) if actuation is not None else \
             [m.name for m in engine.model.motors][:self.plan.n_motors]
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
         B, p = engine.batch_size, self.plan
         new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
         self.q = new(p.nq)
@@ -1538,11 +1327,8 @@ class ReferenceTrajectory:
         self._interval = torch.as_tensor(p.time_interval, dtype=torch.float64, device=engine.device)
         self.time_offset.fill_(float(p.time_interval[0, 0]))
         self._io = _abi.TrajectoryIO()
-        desc, keep = self.plan.desc(np.float64 if engine.dtype == torch.float64 else np.float32)
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_trajectory_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep
+        self.plan.dtype = np.float64 if engine.dtype == torch.float64 else np.float32
+        self._create_plan("trajectory")
 
     @property
     def fieldnames(self):
@@ -1552,14 +1338,6 @@ class ReferenceTrajectory:
     def out_of_range(self) -> torch.Tensor:
         """`[B]` bool: the query time of the lane was out of range in mode "raise" at the last `query`."""
         return (self.status[0] & 1).bool()
-
-    def _mask(self, lane_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        if lane_mask is None:
-            return None
-        mask = lane_mask.to(device=self._eng.device, dtype=torch.uint8).contiguous()
-        if tuple(mask.shape) != (self._eng.batch_size,):
-            raise ValueError(f"lane_mask must have shape ({self._eng.batch_size},)")
-        return mask
 
     def select(self, name_or_indices, lane_mask: Optional[torch.Tensor] = None, time_offset_ratio=0.0) -> None:
         """Select a trajectory by name (every masked lane the same) or by a `[B]` tensor of indices, and set the time offset
@@ -1614,22 +1392,11 @@ class ReferenceTrajectory:
             raise ValueError(f"time must be a contiguous float64 tensor of shape ({eng.batch_size},) on the engine's device")
         mask = self._mask(lane_mask)
         io.time, io.trajectory, io.time_offset = time.data_ptr(), self.trajectory.data_ptr(), self.time_offset.data_ptr()
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = self._ptr(mask, torch.uint8)
         for name in ("q", "v", "a", "command", "odom_pose", "position"):
-            t = getattr(self, name)
-            if t is not None:
-                _check_block_tensor(eng, t)
-            setattr(io, name, None if t is None else t.data_ptr())
+            setattr(io, name, self._ptr(getattr(self, name)))
         io.status = self.status.data_ptr()
         self._check(self._L.jm_block_trajectory_state(self._plan, self._dtype, eng.batch_size, self._C.byref(io), eng._stream()))
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_trajectory_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
 
 def integrate_zoh(state: torch.Tensor, state_min: torch.Tensor, state_max: torch.Tensor,
@@ -1680,7 +1447,7 @@ def tracking_rewards_fieldnames(motor_names):
     return {"value": rows, "reference": list(rows), "rewards": [f"reward_{t}" for t in TRACKING_REWARD_TERMS]}
 
 
-class TrackingRewards:
+class TrackingRewards(_PlanBlock):
     """The tracking rewards of the reference's composition layer on balance quantities per lane: a quantity in
     `QuantityEvalMode.TRUE` against the same quantity in `QuantityEvalMode.REFERENCE` ≙ `TrackingQuantityReward`
     (compositions/generic.py:64-122).  Terms (`TRACKING_REWARD_TERMS`, the rows of `rewards` `[4][B]`): the base height ≙
@@ -1700,7 +1467,6 @@ class TrackingRewards:
     def __init__(self, engine, *, frames=None, reference_frames=None, locomotion=None, reference_locomotion=None, actuation=None,
                  trajectory=None, base_height_cutoff: Optional[float] = None, odometry_velocity_cutoff: Optional[float] = None,
                  capture_point_cutoff: Optional[float] = None, joint_positions_cutoff: Optional[float] = None) -> None:
-        import ctypes as C
         import os
 
         from . import _abi, trackrewards
@@ -1740,23 +1506,15 @@ class TrackingRewards:
         n_motors = 0 if actuation is None else int(actuation.position.shape[0])
         self.plan = trackrewards.build_plan(engine.model, None if frames is None else frames.frame_names,
                                             None if reference_frames is None else reference_frames.frame_names, n_motors)
-        self._C = C
-        self._eng = engine
+        self._bind(engine)
         self._blocks = (frames, reference_frames, locomotion, reference_locomotion, actuation, trajectory)
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
         self.cutoffs = tuple(None if c is None else float(c) for c in cutoffs)
-        self._cutoff = (C.c_double * 4)(*[c or 0.0 for c in self.cutoffs])
+        self._cutoff = (self._C.c_double * 4)(*[c or 0.0 for c in self.cutoffs])
         B = engine.batch_size
         new = lambda rows: torch.zeros((rows, B), dtype=engine.dtype, device=engine.device)      # noqa: E731
         self.value, self.reference, self.rewards = new(self.plan.rows), new(self.plan.rows), new(4)
         self._io = _abi.TrackRewardsIO()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_trackrewards_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("trackrewards")
 
     @property
     def fieldnames(self):
@@ -1767,21 +1525,15 @@ class TrackingRewards:
         return self.rewards[TRACKING_REWARD_TERMS.index(term)]
 
     def _launch(self, mask: Optional[torch.Tensor]) -> None:
-        eng, io = self._eng, self._io
+        eng, io, ptr = self._eng, self._io, self._ptr
         frames, reference_frames, locomotion, reference_locomotion, actuation, trajectory = self._blocks
-
-        def ptr(t: Optional[torch.Tensor]):
-            if t is None:
-                return None
-            _check_block_tensor(eng, t)
-            return t.data_ptr()
         get = lambda blk, name: None if blk is None else ptr(getattr(blk, name))      # noqa: E731
         io.pose, io.pose_reference = get(frames, "pose"), get(reference_frames, "pose")
         io.v_avg, io.quat_no_yaw = get(frames, "average_velocity"), get(frames, "quat_no_yaw")
         io.v_avg_reference, io.quat_no_yaw_reference = get(reference_frames, "average_velocity"), get(reference_frames, "quat_no_yaw")
         io.dcm, io.dcm_reference = get(locomotion, "dcm"), get(reference_locomotion, "dcm")
         io.position, io.position_reference = get(actuation, "position"), get(trajectory, "position")
-        io.lane_mask = None if mask is None else mask.data_ptr()
+        io.lane_mask = ptr(mask, torch.uint8)
         io.value, io.reference, io.rewards = ptr(self.value), ptr(self.reference), ptr(self.rewards)
         self._check(self._L.jm_block_tracking_rewards(self._plan, self._dtype, eng.batch_size, self._C.byref(io), self._cutoff,
                                                       eng._stream()))
@@ -1789,28 +1541,14 @@ class TrackingRewards:
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         """The rewards at the state of a new episode on the masked lanes (every lane without a mask); the other lanes keep
         every tensor bit for bit.  Call it after the reset of every block it reads."""
-        eng = self._eng
-        mask = None
-        if lane_mask is not None:
-            mask = lane_mask.to(device=eng.device, dtype=torch.uint8).contiguous()
-            if tuple(mask.shape) != (eng.batch_size,):
-                raise ValueError(f"lane_mask must have shape ({eng.batch_size},)")
-        self._launch(mask)
+        self._launch(self._mask(lane_mask))
 
     def refresh(self) -> None:
         """One launch on the engine's stream, behind the refresh of every block it reads."""
         self._launch(None)
 
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_trackrewards_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
-
-class Composition:
+class Composition(_PlanBlock):
     """The composition layer of the reference's environments per lane ≙ `ComposedJiminyEnv(reward=..., terminations=[...])`
     (bases/pipeline.py:751-829 over bases/compositions.py, compositions/mixin.py, compositions/generic.py): `reward` is a
     description of `jiminy_amd.compositions` (`RewardTerm`, `SurviveReward`, `AdditiveMixtureReward`,
@@ -1829,7 +1567,6 @@ class Composition:
     tensor bit for bit.  The tensors never change identity."""
 
     def __init__(self, engine, reward=None, terminations=()) -> None:
-        import ctypes as C
         import os
 
         from . import _abi, compositions
@@ -1840,11 +1577,7 @@ class Composition:
         for t in self.plan.sources:
             if t.device != engine.device:
                 raise ValueError("pipeline block tensors must be on the engine's device")
-        self._C = C
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
-        self._dtype = _abi.JM_F64 if engine.dtype == torch.float64 else _abi.JM_F32
+        self._bind(engine)
         self.node_names, self.condition_names = list(self.plan.node_names), list(self.plan.condition_names)
         B = engine.batch_size
         new = lambda *shape, dtype=engine.dtype: torch.zeros((*shape, B), dtype=dtype, device=engine.device)      # noqa: E731
@@ -1855,11 +1588,7 @@ class Composition:
         self._io = _abi.ComposeIO()
         for s, ptr in enumerate(self.plan.source_ptr):
             self._io.source[s] = ptr
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_compose_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("compose")
 
     def info(self) -> Dict[str, torch.Tensor]:
         """≙ the reward's entries of the reference's `info`: the row of `node_value` of every node by name (NaN on the lanes
@@ -1869,37 +1598,21 @@ class Composition:
     def refresh(self, time: torch.Tensor, base_terminated: Optional[torch.Tensor] = None, base_truncated: Optional[torch.Tensor] = None,
                 training: bool = True, lane_mask: Optional[torch.Tensor] = None) -> None:
         eng, io, B = self._eng, self._io, self._eng.batch_size
-
-        def flags(t: Optional[torch.Tensor], name: str):
-            if t is None:
-                return None
-            if t.dtype == torch.bool:
-                t = t.view(torch.uint8)
-            if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != eng.device or tuple(t.shape) != (B,):
-                raise ValueError(f"{name} must be a contiguous bool or uint8 tensor of shape ({B},) on the engine's device")
-            return t
-        if time is not None:
-            _check_block_tensor(eng, time)
-            if tuple(time.shape) != (B,):
-                raise ValueError(f"time must have shape ({B},)")
-        held = [flags(base_terminated, "base_terminated"), flags(base_truncated, "base_truncated"), flags(lane_mask, "lane_mask")]
-        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        io.time, io.base_terminated, io.base_truncated, io.lane_mask = ptr(time), ptr(held[0]), ptr(held[1]), ptr(held[2])
+        time_ptr = self._ptr(time)
+        if time is not None and tuple(time.shape) != (B,):
+            raise ValueError(f"time must have shape ({B},)")
+        # (the views of bool flags are held until the launch is issued)
+        held = [self._flags(base_terminated, "base_terminated"), self._flags(base_truncated, "base_truncated"),
+                self._flags(lane_mask, "lane_mask")]
+        io.time = time_ptr
+        io.base_terminated, io.base_truncated, io.lane_mask = (None if t is None else t.data_ptr() for t in held)
         io.reward, io.node_value = self.reward.data_ptr(), self.node_value.data_ptr() if self.plan.n_nodes else None
         io.terminated, io.truncated = self.terminated.data_ptr(), self.truncated.data_ptr()
         io.trigger, io.violations = self.trigger.data_ptr(), self.violations.data_ptr()
         self._check(self._L.jm_block_compose(self._plan, self._dtype, B, self._C.byref(io), int(bool(training)), eng._stream()))
 
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_compose_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
-
-class ObservationAssembler:
+class ObservationAssembler(_PlanBlock):
     """The observation the learner reads, assembled per lane ≙ `FlattenObservation(StackObservation(NormalizeObservation(
     ScaleObservation(AdaptLayoutObservation(env)))))` (wrappers/observation_layout.py:36-540, scale.py:31-244, normalize.py:49-114,
     observation_stack.py:40-265, flatten.py) as one launch of `jm_block_observe` (csrc/jm_observe.h).  `obs` is the nested
@@ -1913,7 +1626,6 @@ class ObservationAssembler:
     read instead (the data pointers are read at every launch either way).  `reset(lane_mask=None)` zeroes the history."""
 
     def __init__(self, engine, obs, **spec) -> None:
-        import ctypes as C
         import os
 
         from . import _abi, observe
@@ -1925,10 +1637,9 @@ class ObservationAssembler:
         for t in self._leaves:
             if t.device != engine.device:
                 raise ValueError("pipeline block tensors must be on the engine's device")
-        self._C, self._observe = C, observe
-        self._eng = engine
-        self._L = engine._lib.L
-        self._check = engine._lib.check
+        self._bind(engine)
+        self._observe = observe
+        # (input and output dtype of the launch: `_dtype`, the engine's, is not what this block passes)
         code = lambda dt: _abi.JM_F64 if dt == torch.float64 else _abi.JM_F32      # noqa: E731
         self._dtype_in, self._dtype_out = code(self.plan.dtype_in), code(self.plan.dtype_out)
         B = engine.batch_size
@@ -1937,11 +1648,7 @@ class ObservationAssembler:
         observe.check_no_alias(self.out, [(f"observation leaf {p}", t) for p, t in zip(self.plan.source_paths, self._leaves)])
         self._io = _abi.ObserveIO()
         self._io.hist, self._io.out = self.hist.data_ptr(), self.out.data_ptr()
-        desc, keep = self.plan.desc()
-        self._plan = C.c_void_p()
-        with torch.cuda.device(engine.device):
-            self._check(self._L.jm_observe_plan_create(C.byref(desc), C.byref(self._plan)))
-        del keep        # (the library copied the description)
+        self._create_plan("observe")
 
     def reset(self, lane_mask: Optional[torch.Tensor] = None) -> None:
         if lane_mask is None:
@@ -1956,23 +1663,10 @@ class ObservationAssembler:
             if t is not first and (t.shape != first.shape or t.stride() != first.stride() or t.dtype != first.dtype or t.device != first.device):
                 raise ValueError(f"observation leaf {self.plan.source_paths[s]} changed its shape, strides, dtype or device")
             io.source[s] = t.data_ptr()
-        if reset_mask is not None:
-            if reset_mask.dtype == torch.bool:
-                reset_mask = reset_mask.view(torch.uint8)
-            if reset_mask.dtype != torch.uint8 or not reset_mask.is_contiguous() or reset_mask.device != eng.device or \
-                    tuple(reset_mask.shape) != (B,):
-                raise ValueError(f"reset_mask must be a contiguous bool or uint8 tensor of shape ({B},) on the engine's device")
+        reset_mask = self._flags(reset_mask, "reset_mask")
         io.reset_mask = None if reset_mask is None else reset_mask.data_ptr()
         self._check(self._L.jm_block_observe(self._plan, self._dtype_in, self._dtype_out, B, self._C.byref(io), int(bool(shift)),
                                              eng._stream()))
-
-    def __del__(self) -> None:
-        plan, self._plan = getattr(self, "_plan", None), None
-        if plan:
-            try:
-                self._L.jm_observe_plan_destroy(plan)
-            except Exception:       # noqa: BLE001  (interpreter shutdown)
-                pass
 
 
 def pd_controller(encoder_data: torch.Tensor, command_state: torch.Tensor,

@@ -1,7 +1,11 @@
-// jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology: the pipeline
-// blocks (`jm_block_*`), the plans of the two observer families, of the frame kinematics, of the locomotion quantities, of the actuated-joint quantities, of the foot pose quantities, of the tracking windows, of the reference trajectories, of the centroidal quantities of a state, of the tracking rewards, of the support polygon, of the composition layer and of the observation assembly, and the seeding of the generators.  Compiled with the
-// flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation unit of its own so
-// that the physics kernels of jm_lib.cpp are compiled without it.
+// jm_lib_blocks.cpp -- the part of the C ABI (include/jiminy_hip.h) that does not depend on the topology:
+//   * the per-tick pipeline blocks and the sensor / model-bias blocks (`jm_block_*` without a plan);
+//   * the plan-backed blocks: `jm_<family>_plan_create / _destroy` and the launches behind them, for the families deform,
+//     attitude, frames, locomotion, actuation, footposes, tracking, trajectory, centroidal, trackrewards, support, compose
+//     and observe (one `jm_<family>.h` each holds the pack function and the kernel);
+//   * the seeding of the generators.
+// Compiled with the flags of jm_lib.cpp and linked into every topology library (jiminy_amd/codegen.py), in a translation
+// unit of its own so that the physics kernels of jm_lib.cpp are compiled without it.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -82,49 +86,57 @@ template<class Plan, class Desc, class Pack> int32_t plan_create(const std::stri
     *out = p;
     return JM_OK;
 }
+// what every plan holds; a family with more state adds members
+struct PlanBase
+{
+    DevicePlan dev;
+};
+
+template<class Plan> int32_t plan_destroy(Plan * p)
+{
+    delete p;
+    return JM_OK;
+}
+
+// the checks every launch starts with, in this order: a null argument (`given` false), a bad size (`sizes_ok` false), a dtype
+// that is neither JM_F64 nor JM_F32.  JM_OK when all pass; the message is built on failure only.
+int32_t check_call(const char * who, bool given, bool sizes_ok, int32_t dtype)
+{
+    const char * what = !given ? ": null argument" : !sizes_ok ? ": bad sizes" : (dtype != JM_F64 && dtype != JM_F32) ? ": bad dtype" : nullptr;
+    return what ? fail(JM_EINVAL, std::string(who) + what) : JM_OK;
+}
+
+// the pointers of a `jm_locomotion_io` in the scalar type of the launch (the ground members keep their defaults)
+template<class T> jm::LocoIO<T> loco_io(const jm_locomotion_io * io)
+{
+    return {(const T *)io->centroidal, (const T *)io->q_root, (const T *)io->model_lane, (const T *)io->con_lambda,
+            io->con_flags, (const T *)io->v_avg, (const T *)io->quat_no_yaw, (const T *)io->pose, io->lane_mask,
+            (T *)io->com, (T *)io->vcom, (T *)io->odom_pose, (T *)io->zmp, (T *)io->dcm, (T *)io->h_angular,
+            (T *)io->contact_force_rel, (T *)io->foot_force_vertical, (T *)io->scalars};
+}
 }  // namespace
 
-// ---- DeformationEstimator, attitude observers (MahonyFilter options, BodyObserver): a plan is validated, packed and
-// uploaded once; every call is one launch
-struct jm_deform_plan
+// ---- the opaque plan types of include/jiminy_hip.h: validated, packed and uploaded once; every call is one launch
+struct jm_deform_plan : PlanBase
 {
-    DevicePlan dev;
     int n_imu = 0, n_flex = 0, ignore_twist = 0;
 };
-struct jm_attitude_plan
+struct jm_attitude_plan : PlanBase
 {
-    DevicePlan dev;
     int n_imu = 0;
 };
-// frame kinematics and its step average (jm_frames.h)
-struct jm_frames_plan
+struct jm_frames_plan : PlanBase {};
+struct jm_locomotion_plan : PlanBase {};
+struct jm_actuation_plan : PlanBase {};
+struct jm_footposes_plan : PlanBase {};
+struct jm_tracking_plan : PlanBase {};
+struct jm_centroidal_plan : PlanBase {};
+struct jm_trackrewards_plan : PlanBase {};
+struct jm_support_plan : PlanBase {};
+struct jm_compose_plan : PlanBase {};
+// the reference trajectories: the samples `[S][R]` in the plan's dtype next to the tables
+struct jm_trajectory_plan : PlanBase
 {
-    DevicePlan dev;
-};
-// the locomotion quantities (jm_locomotion.h)
-struct jm_locomotion_plan
-{
-    DevicePlan dev;
-};
-// the actuated-joint quantities (jm_actuation.h)
-struct jm_actuation_plan
-{
-    DevicePlan dev;
-};
-// the foot pose quantities (jm_footposes.h)
-struct jm_footposes_plan
-{
-    DevicePlan dev;
-};
-// the tracking windows (jm_tracking.h)
-struct jm_tracking_plan
-{
-    DevicePlan dev;
-};
-// the reference trajectories (jm_trajectory.h): the tables and the samples `[S][R]` in the plan's dtype
-struct jm_trajectory_plan
-{
-    DevicePlan dev;
     void * data = nullptr;
     int32_t dtype = 0;
     ~jm_trajectory_plan()
@@ -132,35 +144,9 @@ struct jm_trajectory_plan
         if (data) (void)hipFree(data);
     }
 };
-
-// the centroidal quantities of a state (jm_centroidal.h)
-struct jm_centroidal_plan
+// the observation assembly: the integer table stays on the host as well, for the aliasing check of a launch
+struct jm_observe_plan : PlanBase
 {
-    DevicePlan dev;
-};
-
-// the tracking rewards (jm_trackrewards.h)
-struct jm_trackrewards_plan
-{
-    DevicePlan dev;
-};
-
-// the projected support polygon (jm_support.h)
-struct jm_support_plan
-{
-    DevicePlan dev;
-};
-
-// the composition layer (jm_compose.h)
-struct jm_compose_plan
-{
-    DevicePlan dev;
-};
-
-// the observation assembly (jm_observe.h): the integer table stays on the host as well, for the aliasing check of a launch
-struct jm_observe_plan
-{
-    DevicePlan dev;
     std::vector<int32_t> it;
 };
 
@@ -196,9 +182,7 @@ int32_t jm_block_pd_controller(int32_t dtype, int64_t B, int32_t M, const void *
 int32_t jm_block_mahony_filter(int32_t dtype, int64_t B, int32_t n_imu, const void * imu, void * quat, void * omega,
                                void * cf, void * bias, double kp, double ki, double dt, void * stream)
 {
-    if (!imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_filter: null argument");
-    if (B <= 0 || n_imu <= 0) return fail(JM_EINVAL, "jm_block_mahony_filter: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_filter: bad dtype");
+    if (const int32_t rc = check_call("jm_block_mahony_filter", imu && quat && omega && cf && bias, B > 0 && n_imu > 0, dtype)) return rc;
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
         using T = decltype(z);
         hipLaunchKernelGGL((jm::k_mahony<T>), grid, dim3(256), 0, s, n_imu, (const T *)imu, (T *)quat,
@@ -233,10 +217,8 @@ int32_t jm_block_motor_safety_limit(int32_t dtype, int64_t B, int32_t M, const v
                                     const void * command, const double * kp, const double * kd, const double * soft_lo,
                                     const double * soft_hi, const double * vel_lim, const double * eff_lim, void * out, void * stream)
 {
-    if (!encoder || !encoder_index || !command || !kp || !kd || !soft_lo || !soft_hi || !vel_lim || !eff_lim || !out)
-        return fail(JM_EINVAL, "jm_block_motor_safety_limit: null argument");
-    if (B <= 0 || M <= 0 || M > JM_BLOCK_MAX_MOTORS) return fail(JM_EINVAL, "jm_block_motor_safety_limit: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_motor_safety_limit: bad dtype");
+    const bool given = encoder && encoder_index && command && kp && kd && soft_lo && soft_hi && vel_lim && eff_lim && out;
+    if (const int32_t rc = check_call("jm_block_motor_safety_limit", given, B > 0 && M > 0 && M <= JM_BLOCK_MAX_MOTORS, dtype)) return rc;
     jm::SafetyParams p;
     std::memset(&p, 0, sizeof(p));
     p.M = M;
@@ -261,18 +243,12 @@ int32_t jm_deform_plan_create(const jm_deform_desc * desc, jm_deform_plan ** out
     return JM_OK;
 }
 
-int32_t jm_deform_plan_destroy(jm_deform_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_deform_plan_destroy(jm_deform_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_deformation_estimator(const jm_deform_plan * p, int32_t dtype, int64_t B, const void * encoder,
                                        const void * imu_quat, void * out_quat, void * out_rpy, void * stream)
 {
-    if (!p || !encoder || !imu_quat || !out_quat) return fail(JM_EINVAL, "jm_block_deformation_estimator: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_deformation_estimator: bad dtype");
+    if (const int32_t rc = check_call("jm_block_deformation_estimator", p && encoder && imu_quat && out_quat, B > 0, dtype)) return rc;
     const jm::DeformArgs a{p->dev.it, p->dev.dt, p->n_imu, p->n_flex, p->ignore_twist};
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
         using T = decltype(z);
@@ -289,19 +265,13 @@ int32_t jm_attitude_plan_create(const jm_attitude_desc * desc, jm_attitude_plan 
     return JM_OK;
 }
 
-int32_t jm_attitude_plan_destroy(jm_attitude_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_attitude_plan_destroy(jm_attitude_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_attitude_init(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * q, const void * imu,
                                const uint8_t * lane_mask, int32_t exact_init, void * quat, void * omega, void * cf, void * bias,
                                void * twist, void * rpy, void * stream)
 {
-    if (!p || !q || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_attitude_init: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_attitude_init: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_attitude_init: bad dtype");
+    if (const int32_t rc = check_call("jm_block_attitude_init", p && q && imu && quat && omega && cf && bias, B > 0, dtype)) return rc;
     const jm::AttitudeArgs a{p->dev.it, p->dev.dt, p->n_imu};
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
         using T = decltype(z);
@@ -314,9 +284,7 @@ int32_t jm_block_attitude_init(const jm_attitude_plan * p, int32_t dtype, int64_
 int32_t jm_block_mahony_observer(const jm_attitude_plan * p, int32_t dtype, int64_t B, const void * imu, void * quat, void * omega,
                                  void * cf, void * bias, double dt, int32_t ignore_twist, void * rpy, void * stream)
 {
-    if (!p || !imu || !quat || !omega || !cf || !bias) return fail(JM_EINVAL, "jm_block_mahony_observer: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_mahony_observer: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_mahony_observer: bad dtype");
+    if (const int32_t rc = check_call("jm_block_mahony_observer", p && imu && quat && omega && cf && bias, B > 0, dtype)) return rc;
     const jm::AttitudeArgs a{p->dev.it, p->dev.dt, p->n_imu};
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
         using T = decltype(z);
@@ -329,9 +297,7 @@ int32_t jm_block_body_observer(const jm_attitude_plan * p, int32_t dtype, int64_
                                void * quat, void * omega, void * twist, int32_t twist_mode, double time_constant_inv, double dt,
                                void * rpy, void * stream)
 {
-    if (!p || !imu_quat || !imu_omega || !quat || !omega) return fail(JM_EINVAL, "jm_block_body_observer: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_body_observer: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_body_observer: bad dtype");
+    if (const int32_t rc = check_call("jm_block_body_observer", p && imu_quat && imu_omega && quat && omega, B > 0, dtype)) return rc;
     if (twist_mode < 0 || twist_mode > 2) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode must be 0, 1 or 2");
     if (twist_mode == 2 && !twist) return fail(JM_EINVAL, "jm_block_body_observer: twist_mode 2 needs the twist state");
     if (quat == imu_quat) return fail(JM_EINVAL, "jm_block_body_observer: quat must not alias imu_quat");
@@ -349,11 +315,7 @@ int32_t jm_frames_plan_create(const jm_frames_desc * desc, jm_frames_plan ** out
     return plan_create("jm_frames_plan_create", desc, out, jm::frames_pack);
 }
 
-int32_t jm_frames_plan_destroy(jm_frames_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_frames_plan_destroy(jm_frames_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_frame_kinematics(const jm_frames_plan * p, int32_t dtype, int64_t B, const void * q, const void * v,
                                   const void * model_lane, const uint8_t * lane_mask, void * pose, void * pose_prev, void * rpy,
@@ -375,9 +337,7 @@ int32_t jm_block_frame_kinematics(const jm_frames_plan * p, int32_t dtype, int64
 int32_t jm_block_frame_average(const jm_frames_plan * p, int32_t dtype, int64_t B, void * pose_prev, const void * pose,
                                double inv_step_dt, void * v_avg, void * pose_mean, void * quat_no_yaw, void * stream)
 {
-    if (!p || !pose_prev || !pose) return fail(JM_EINVAL, "jm_block_frame_average: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_frame_average: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_frame_average: bad dtype");
+    if (const int32_t rc = check_call("jm_block_frame_average", p && pose_prev && pose, B > 0, dtype)) return rc;
     if (pose_prev == pose) return fail(JM_EINVAL, "jm_block_frame_average: pose_prev must not alias pose");
     const jm::FramesArgs a{p->dev.it, p->dev.dt};
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
@@ -392,26 +352,17 @@ int32_t jm_locomotion_plan_create(const jm_locomotion_desc * desc, jm_locomotion
     return plan_create("jm_locomotion_plan_create", desc, out, jm::locomotion_pack);
 }
 
-int32_t jm_locomotion_plan_destroy(jm_locomotion_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_locomotion_plan_destroy(jm_locomotion_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_locomotion(const jm_locomotion_plan * p, int32_t dtype, int64_t B, const jm_locomotion_io * io,
                             double momentum_cutoff, double friction_cutoff, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_locomotion: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_locomotion: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_locomotion: bad dtype");
+    if (const int32_t rc = check_call("jm_block_locomotion", p && io, B > 0, dtype)) return rc;
     const int32_t * it = p->dev.it;
     const double * dt = p->dev.dt;
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
         using T = decltype(z);
-        const jm::LocoIO<T> a{(const T *)io->centroidal, (const T *)io->q_root, (const T *)io->model_lane, (const T *)io->con_lambda,
-                              io->con_flags, (const T *)io->v_avg, (const T *)io->quat_no_yaw, (const T *)io->pose, io->lane_mask,
-                              (T *)io->com, (T *)io->vcom, (T *)io->odom_pose, (T *)io->zmp, (T *)io->dcm, (T *)io->h_angular,
-                              (T *)io->contact_force_rel, (T *)io->foot_force_vertical, (T *)io->scalars};
+        const jm::LocoIO<T> a = loco_io<T>(io);
         hipLaunchKernelGGL((jm::k_locomotion<T>), grid, dim3(256), 0, s, it, dt, a, momentum_cutoff, friction_cutoff, (long long)B);
     });
 }
@@ -419,19 +370,14 @@ int32_t jm_block_locomotion(const jm_locomotion_plan * p, int32_t dtype, int64_t
 int32_t jm_block_locomotion_ground(const jm_locomotion_plan * p, int32_t dtype, int64_t B, const jm_locomotion_io * io,
                                    const jm_locomotion_ground * g, double momentum_cutoff, double friction_cutoff, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_locomotion_ground: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_locomotion_ground: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_locomotion_ground: bad dtype");
+    if (const int32_t rc = check_call("jm_block_locomotion_ground", p && io, B > 0, dtype)) return rc;
     std::string why;
     if (!jm::locomotion_ground_check(g, io, why)) return fail(JM_EINVAL, why);
     const int32_t * it = p->dev.it;
     const double * dt = p->dev.dt;
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
         using T = decltype(z);
-        jm::LocoIO<T> a{(const T *)io->centroidal, (const T *)io->q_root, (const T *)io->model_lane, (const T *)io->con_lambda,
-                        io->con_flags, (const T *)io->v_avg, (const T *)io->quat_no_yaw, (const T *)io->pose, io->lane_mask,
-                        (T *)io->com, (T *)io->vcom, (T *)io->odom_pose, (T *)io->zmp, (T *)io->dcm, (T *)io->h_angular,
-                        (T *)io->contact_force_rel, (T *)io->foot_force_vertical, (T *)io->scalars};
+        jm::LocoIO<T> a = loco_io<T>(io);
         if (!g || !g->heights)
         {
             // flat ground: the kernel of jm_block_locomotion itself, so that the outputs are equal bit for bit
@@ -454,18 +400,12 @@ int32_t jm_actuation_plan_create(const jm_actuation_desc * desc, jm_actuation_pl
     return plan_create("jm_actuation_plan_create", desc, out, jm::actuation_pack);
 }
 
-int32_t jm_actuation_plan_destroy(jm_actuation_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_actuation_plan_destroy(jm_actuation_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_actuation(const jm_actuation_plan * p, int32_t dtype, int64_t B, const jm_actuation_io * io, int32_t mode,
                            int32_t motor_side, double position_margin, double velocity_max, double power_cutoff, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_actuation: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_actuation: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_actuation: bad dtype");
+    if (const int32_t rc = check_call("jm_block_actuation", p && io, B > 0, dtype)) return rc;
     if (mode != jm::ACT_RESTART && mode != jm::ACT_PUSH) return fail(JM_EINVAL, "jm_block_actuation: mode must be 0 (restart) or 1 (push)");
     const int32_t * it = p->dev.it;
     const double * dt = p->dev.dt;
@@ -484,18 +424,12 @@ int32_t jm_footposes_plan_create(const jm_footposes_desc * desc, jm_footposes_pl
     return plan_create("jm_footposes_plan_create", desc, out, jm::footposes_pack);
 }
 
-int32_t jm_footposes_plan_destroy(jm_footposes_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_footposes_plan_destroy(jm_footposes_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_foot_poses(const jm_footposes_plan * p, int32_t dtype, int64_t B, const jm_footposes_io * io, double position_cutoff,
                             double orientation_cutoff, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_foot_poses: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_foot_poses: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_foot_poses: bad dtype");
+    if (const int32_t rc = check_call("jm_block_foot_poses", p && io, B > 0, dtype)) return rc;
     const int32_t * it = p->dev.it;
     const double * dt = p->dev.dt;
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
@@ -511,18 +445,12 @@ int32_t jm_tracking_plan_create(const jm_tracking_desc * desc, jm_tracking_plan 
     return plan_create("jm_tracking_plan_create", desc, out, jm::tracking_pack);
 }
 
-int32_t jm_tracking_plan_destroy(jm_tracking_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_tracking_plan_destroy(jm_tracking_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_tracking(const jm_tracking_plan * p, int32_t dtype, int64_t B, const jm_tracking_io * io, int32_t mode,
                           double odometry_cutoff, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_tracking: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_tracking: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_tracking: bad dtype");
+    if (const int32_t rc = check_call("jm_block_tracking", p && io, B > 0, dtype)) return rc;
     if (mode != jm::TRK_RESTART && mode != jm::TRK_PUSH) return fail(JM_EINVAL, "jm_block_tracking: mode must be 0 (restart) or 1 (push)");
     const int32_t * it = p->dev.it;
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
@@ -554,17 +482,11 @@ int32_t jm_trajectory_plan_create(const jm_trajectory_desc * desc, jm_trajectory
     return JM_OK;
 }
 
-int32_t jm_trajectory_plan_destroy(jm_trajectory_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_trajectory_plan_destroy(jm_trajectory_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_trajectory_state(const jm_trajectory_plan * p, int32_t dtype, int64_t B, const jm_trajectory_io * io, void * stream)
 {
-    if (!p || !io || !io->time || !io->trajectory || !io->time_offset) return fail(JM_EINVAL, "jm_block_trajectory_state: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_trajectory_state: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_trajectory_state: bad dtype");
+    if (const int32_t rc = check_call("jm_block_trajectory_state", p && io && io->time && io->trajectory && io->time_offset, B > 0, dtype)) return rc;
     if (dtype != p->dtype) return fail(JM_EINVAL, "jm_block_trajectory_state: dtype is not the one the plan was created with");
     const int32_t * it = p->dev.it;
     const double * dt = p->dev.dt;
@@ -582,18 +504,12 @@ int32_t jm_centroidal_plan_create(const jm_centroidal_desc * desc, jm_centroidal
     return plan_create("jm_centroidal_plan_create", desc, out, jm::centroidal_pack);
 }
 
-int32_t jm_centroidal_plan_destroy(jm_centroidal_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_centroidal_plan_destroy(jm_centroidal_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_centroidal_state(const jm_centroidal_plan * p, int32_t dtype, int64_t B, const void * q, const void * v,
                                   const void * a, const uint8_t * lane_mask, void * centroidal, void * stream)
 {
-    if (!p || !q || !v) return fail(JM_EINVAL, "jm_block_centroidal_state: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_centroidal_state: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_centroidal_state: bad dtype");
+    if (const int32_t rc = check_call("jm_block_centroidal_state", p && q && v, B > 0, dtype)) return rc;
     if (!centroidal) return JM_OK;      // (the only output is absent: nothing is written)
     const jm::FramesArgs args{p->dev.it, p->dev.dt};
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
@@ -608,18 +524,12 @@ int32_t jm_trackrewards_plan_create(const jm_trackrewards_desc * desc, jm_trackr
     return plan_create("jm_trackrewards_plan_create", desc, out, jm::trackrewards_pack);
 }
 
-int32_t jm_trackrewards_plan_destroy(jm_trackrewards_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_trackrewards_plan_destroy(jm_trackrewards_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_tracking_rewards(const jm_trackrewards_plan * p, int32_t dtype, int64_t B, const jm_trackrewards_io * io,
                                   const double * cutoff, void * stream)
 {
-    if (!p || !io || !cutoff) return fail(JM_EINVAL, "jm_block_tracking_rewards: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_tracking_rewards: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_tracking_rewards: bad dtype");
+    if (const int32_t rc = check_call("jm_block_tracking_rewards", p && io && cutoff, B > 0, dtype)) return rc;
     jm::TrkRewCutoffs c;
     for (int k = 0; k < jm::TR_TERMS; ++k) c.c[k] = cutoff[k] > 0.0 ? cutoff[k] : 0.0;     // (NaN: skipped as well)
     const int32_t * it = p->dev.it;
@@ -638,18 +548,12 @@ int32_t jm_support_plan_create(const jm_support_desc * desc, jm_support_plan ** 
     return plan_create("jm_support_plan_create", desc, out, jm::support_pack);
 }
 
-int32_t jm_support_plan_destroy(jm_support_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_support_plan_destroy(jm_support_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_support_polygon(const jm_support_plan * p, int32_t dtype, int64_t B, const jm_support_io * io, double cutoff_inner,
                                  double cutoff_outer, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_support_polygon: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_support_polygon: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_support_polygon: bad dtype");
+    if (const int32_t rc = check_call("jm_block_support_polygon", p && io, B > 0, dtype)) return rc;
     std::string why;
     if (!jm::support_cutoffs_check(cutoff_inner, cutoff_outer, why)) return fail(JM_EINVAL, why);
     const int32_t * it = p->dev.it;
@@ -666,17 +570,11 @@ int32_t jm_compose_plan_create(const jm_compose_desc * desc, jm_compose_plan ** 
     return plan_create("jm_compose_plan_create", desc, out, jm::compose_pack);
 }
 
-int32_t jm_compose_plan_destroy(jm_compose_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_compose_plan_destroy(jm_compose_plan * p) { return plan_destroy(p); }
 
 int32_t jm_block_compose(const jm_compose_plan * p, int32_t dtype, int64_t B, const jm_compose_io * io, int32_t training, void * stream)
 {
-    if (!p || !io) return fail(JM_EINVAL, "jm_block_compose: null argument");
-    if (B <= 0) return fail(JM_EINVAL, "jm_block_compose: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_compose: bad dtype");
+    if (const int32_t rc = check_call("jm_block_compose", p && io, B > 0, dtype)) return rc;
     const int32_t * it = p->dev.it;
     const double * dt = p->dev.dt;
     return launch_lanes(dtype, B, 1, stream, [&](auto z, dim3 grid, hipStream_t s) {
@@ -706,11 +604,7 @@ int32_t jm_observe_plan_create(const jm_observe_desc * desc, jm_observe_plan ** 
     return rc;
 }
 
-int32_t jm_observe_plan_destroy(jm_observe_plan * p)
-{
-    delete p;
-    return JM_OK;
-}
+int32_t jm_observe_plan_destroy(jm_observe_plan * p) { return plan_destroy(p); }
 
 // ≙ one `transform_observation` of the whole chain: `_array_scale` per scale operation (scale.py:236-244), the affine map of
 // normalize.py:92-114, the shift and the write of observation_stack.py:225-265 and the concatenation of flatten.py
@@ -840,9 +734,8 @@ int32_t jm_block_sensor_delay(int32_t dtype, int64_t B, int32_t n_sensors, int32
 int32_t jm_block_model_bias(int32_t dtype, int64_t B, int32_t njoints, int32_t first_joint, const double * nominal,
                             const float * std4, uint64_t * rng_state, const uint8_t * mask, void * model_lane, void * stream)
 {
-    if (!nominal || !std4 || !rng_state || !model_lane) return fail(JM_EINVAL, "jm_block_model_bias: null argument");
-    if (B <= 0 || njoints < 1 || first_joint < 1 || first_joint > njoints) return fail(JM_EINVAL, "jm_block_model_bias: bad sizes");
-    if (dtype != JM_F64 && dtype != JM_F32) return fail(JM_EINVAL, "jm_block_model_bias: bad dtype");
+    const bool sizes_ok = B > 0 && njoints >= 1 && first_joint >= 1 && first_joint <= njoints;
+    if (const int32_t rc = check_call("jm_block_model_bias", nominal && std4 && rng_state && model_lane, sizes_ok, dtype)) return rc;
     for (int i = 0; i < 4; ++i)
         if (!(std4[i] >= 0.0f)) return fail(JM_EINVAL, "jm_block_model_bias: negative standard deviation");
     jm::BiasParams p{};

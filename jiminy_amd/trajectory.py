@@ -183,13 +183,14 @@ class TrajectoryPlan:
     n_command: int
     n_motors: int
     arrays: Dict[str, Any] = field(default_factory=dict)
+    dtype: Any = np.float64                      # of the samples on the device: the block sets its engine's
 
     @property
     def n_trajectories(self) -> int:
         return len(self.names)
 
-    def desc(self, dtype) -> Tuple["_abi.TrajectoryDesc", List[np.ndarray]]:
-        return make_desc(dtype=dtype, **self.arrays)
+    def desc(self, dtype=None) -> Tuple["_abi.TrajectoryDesc", List[np.ndarray]]:
+        return make_desc(dtype=dtype or self.dtype, **self.arrays)
 
 
 def _check_quaternions(name: str, q: np.ndarray, kinds: Sequence[int], rows: Sequence[int]) -> None:
